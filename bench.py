@@ -14,11 +14,21 @@ identical labels) -- every GEMM in split-f16 arithmetic on the f16 matrix cores 
 norms / softmax / attention.  The bf16 mode is ~2.2x faster but does not meet that bar on this network, so it is
 reported as a side line (`other_modes`), never as `value`.
 
-Prints ONE JSON line (rank 0).  `roofline` describes the dominant kernel -- the un-split bf16 MFMA GEMM instantiation with the
-largest share of the step -- from HIP events (on the launch stream) around every C-ABI launch in extra, instrumented eager steps
-after the timed region; `traffic` = its HBM bytes per launch from the committed rocprofv3 PMC passes of this workload
-(profiles/r01_pmc_hbm_traffic.json).  `cpu_baseline` is the oracle (CPU restatement of the reference, fp32) timed on this host
-for one image of the same workload; `parity_vs_cpu_oracle` compares the timed run's last result with it.
+Prints ONE JSON line (rank 0).  A plain run sets up, warms up, times `--steps` steps, writes the last timed step's outputs if
+`--dump-outputs DIR` is given, and prints the line: `value` (images/s), `ms_per_step` (wall time of one timed step) and the run's
+configuration.  Everything else is measured only with `--full` (these fields of the line are null without it):
+  gpu_ms_per_step   K more steps without the host read-back, bracketed by events on the launch stream;
+  two_in_flight     two model instances driven from two host threads on two streams;
+  other_modes       the varied-input streams, the exact-fp32 and the bf16 modes on the same image;
+  roofline          the dominant kernel -- the un-split bf16 MFMA GEMM instantiation with the largest share of the step -- from HIP events
+                    (on the launch stream) around every C-ABI launch in extra, instrumented eager steps after the timed region; `traffic` =
+                    its HBM bytes per launch from the committed rocprofv3 PMC passes of this workload (profiles/r06_pmc_hbm_traffic.json).
+                    `--breakdown FILE` runs these instrumented steps too;
+  cpu_baseline      the oracle (CPU restatement of the reference, fp32) timed on this host for one image of the same workload;
+  parity_vs_cpu_oracle   the timed run's last result (and `--parity-seeds` more inputs) compared with the oracle.
+
+`--dump-outputs DIR` writes, after the timed steps, what the timed path's last step returned to its caller (rank 0's image) as
+DIR/<name>.npy in float32 / float64 (see dump_outputs).  Weights and inputs are seeded, so the same arguments give the same inputs.
 """
 import argparse
 import json
@@ -128,11 +138,67 @@ def varied_streams(model, cfg, size, n_panoptic, fixed_images_per_s):
     return out
 
 
+DUMP_FULL_BYTES = 8 << 20      # --dump-outputs: an array up to this size is written whole ...
+DUMP_PIXELS = 1 << 15          # ... a larger one at this many seeded pixel positions of each of its (H, W) planes
+DUMP_MAX_BYTES = 64 << 20
+
+
+def dump_outputs(res, out_dir):
+    """--dump-outputs: one eval_seg result, as its caller receives it, into out_dir/<name>.npy.  Names follow the result's structure:
+    mask_pred, sem_seg, instances_<field> (pred_masks, scores, pred_classes, query_index, pred_boxes), panoptic_seg_0 (the id map) and
+    panoptic_seg_1 (segments_info as rows of its fields in sorted key order: category_id, id, isthing).  Float64 and integer data are
+    written as float64, everything else as float32.  An array over DUMP_FULL_BYTES is written as (planes, DUMP_PIXELS): the values at a
+    fixed seeded sample of flat pixel positions (y * W + x, in <name>__pixels.npy) of each of its (H, W) planes, and <name>__plane_sum.npy
+    holds every plane's sum over ALL its pixels in float64, so a difference anywhere in a plane shows."""
+    import numpy as np
+
+    def leaves(name, v):
+        if torch.is_tensor(v):
+            yield name, v
+        elif isinstance(v, dict):
+            for k, x in v.items():
+                yield from leaves(f"{name}_{k}" if name else str(k), x)
+        elif hasattr(v, "get_fields"):                                      # psalm_amd.model.Instances
+            yield from leaves(name, v.get_fields())
+        elif isinstance(v, list) and all(isinstance(x, dict) for x in v):  # a table of records (an empty one too): (rows, fields)
+            keys = sorted(v[0]) if v else []
+            yield name, torch.tensor([[float(x[k]) for k in keys] for x in v], dtype=torch.float64).reshape(len(v), len(keys))
+        elif isinstance(v, (list, tuple)):
+            for i, x in enumerate(v):
+                yield from leaves(f"{name}_{i}", x)
+
+    arrays = {}
+    for name, t in leaves("", res):
+        t = t.detach()
+        dt = torch.float64 if t.dtype == torch.float64 or not (t.is_floating_point() or t.dtype == torch.bool) else torch.float32
+        esz = 8 if dt == torch.float64 else 4
+        if t.dim() >= 2 and t.numel() * esz > DUMP_FULL_BYTES:
+            hw = t.shape[-2] * t.shape[-1]
+            planes = t.reshape(-1, hw)
+            pix = torch.randperm(hw, generator=torch.Generator().manual_seed(0))[:DUMP_PIXELS].sort().values
+            arrays[name] = planes.index_select(1, pix.to(t.device)).to(dt).cpu().numpy()
+            arrays[name + "__pixels"] = pix.to(torch.float64).numpy()
+            arrays[name + "__plane_sum"] = planes.to(torch.float64).sum(1).cpu().numpy()
+        else:
+            arrays[name] = t.to(dt).cpu().numpy()
+    total = sum(a.nbytes for a in arrays.values())
+    if total > DUMP_MAX_BYTES:
+        raise SystemExit(f"bench.py: --dump-outputs would write {total} bytes (> {DUMP_MAX_BYTES})")
+    os.makedirs(out_dir, exist_ok=True)
+    for name, a in arrays.items():
+        np.save(os.path.join(out_dir, name + ".npy"), a)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
-    ap.add_argument("--steps", type=int, default=10)
+    ap.add_argument("--steps", type=int, default=10, help="timed steps (>= 1)")
     ap.add_argument("--warmup", type=int, default=3)
+    ap.add_argument("--full", action="store_true",
+                    help="also run every side measurement (GPU-only time, two in flight, varied streams, instrumented roofline steps, CPU baseline, "
+                         "parity vs the CPU oracle, fp32 / bf16 side modes); a plain run times the headline steps only")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="write the last timed step's outputs (rank 0) as DIR/<name>.npy, float32 / float64, <= 64 MB in all")
     ap.add_argument("--size", type=int, default=1024)
     ap.add_argument("--precision", default="f16x3", choices=["f16x3", "bf16", "fp32"])
     ap.add_argument("--no-side-modes", action="store_true", help="skip the bf16 side-line measurement (rank 0, N=1 only)")
@@ -156,6 +222,8 @@ def main():
                          "script's launcher / affinity / placeholder-rank / broadcast / checksum / all_gather / one-JSON-line path for N > 1 on a "
                          "machine without GPUs.  Its numbers mean nothing; the line says \"emu\": true")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be >= 1")
     emu = args.emu
 
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
@@ -275,11 +343,13 @@ def main():
     barrier()
     dt = time.perf_counter() - t0
     model_graph_stats = dict(model.graph_stats) if not args.eager else None
+    if args.dump_outputs and rank == 0:
+        dump_outputs(out[0], args.dump_outputs)
     # The parity leg compares the TIMED loop's own last result with the oracle.  With graph_outputs = "alias" that result's `mask_pred` is
     # the captured graph's own buffer, which every later replay through this model overwrites (the varied-stream leg feeds OTHER inputs:
     # r05a compared seed 0's oracle with the last varied image) -- so it is copied here, right behind the timed region.
     timed_out = None
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:
+    if args.full and rank == 0 and world == 1 and not args.no_cpu_baseline:
         o_ = out[0]
         timed_out = [{"mask_pred": o_["mask_pred"].clone(), "sem_seg": o_["sem_seg"].clone(),
                       "panoptic_seg": (o_["panoptic_seg"][0].clone(), list(o_["panoptic_seg"][1]))}]
@@ -295,7 +365,7 @@ def main():
     # (`_finalize` replaced by a pass-through: graph replay + the crop / resize / inference tail, nothing the host waits for), bracketed by
     # events on the launch stream; `ms_per_step` - `gpu_ms_per_step` is what prompt handling, the blob upload and the result read-back add
     gpu_ms = None
-    if not args.eager and rank == 0 and not emu:
+    if args.full and not args.eager and rank == 0 and not emu:
         e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
         model._finalize = lambda r_, info_: r_
         try:
@@ -314,7 +384,7 @@ def main():
     # at a time); a serving loop can drive a second `PSALM.replica()` (shared weights, own buffers / graphs) from a second host thread on a
     # second stream, and the hardware fills one image's partial waves and latency-bound launches with the other's (r03a: +11 %).
     inflight = None
-    if rank == 0 and world == 1 and not args.eager and not args.no_side_modes and args.precision == "f16x3" and not emu:
+    if args.full and rank == 0 and world == 1 and not args.eager and not args.no_side_modes and args.precision == "f16x3" and not emu:
         try:                                                    # an auxiliary leg must never cost the run its JSON line
             import threading
             rep = model.replica()
@@ -360,7 +430,7 @@ def main():
 
     # ---- side metric, NOT `value`: does the throughput hold on a stream the reference's evaluation loops would feed?  (VERDICT r04 missing #2)
     varied = None
-    if rank == 0 and world == 1 and not args.eager and not args.no_varied and not emu and args.precision == "f16x3":
+    if args.full and rank == 0 and world == 1 and not args.eager and not args.no_varied and not emu and args.precision == "f16x3":
         try:
             varied = varied_streams(model, cfg, args.size, args.varied_n, fixed_images_per_s=args.steps / dt)
         except Exception as ex:  # noqa: BLE001  (auxiliary leg)
@@ -370,7 +440,7 @@ def main():
     # ---- instrumented steps (not part of `value`): HIP events (torch's current stream = the launch stream) around every
     # C-ABI launch, attributed to kernel instantiations through psalm_gemm_describe (the library's own selection function)
     roof = None
-    if rank == 0 and not emu:
+    if (args.full or args.breakdown) and rank == 0 and not emu:
         recs = []
         model.use_graphs = False                                  # per-launch events need the eager launch path
         model.overlap_streams = False                             # ... and one stream: the timed region runs the pixel decoder concurrently with
@@ -540,7 +610,7 @@ def main():
     parity = None
     side = None
     side_fp32 = None
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:
+    if args.full and rank == 0 and world == 1 and not args.no_cpu_baseline:
         from oracle import psalm_oracle as O
         cores = min(os.cpu_count() or 1, 16)                     # default when no sweep file is present
         sweep = None

@@ -23,7 +23,7 @@ from psalm_amd.synthetic import make_inputs, make_state_dict
 
 pytestmark = pytest.mark.gpu
 EXACT = ("fp32", "f16x3")      # fp32-class modes: asserted at the fp32 tolerances (f16x3 = split-f16 GEMMs, 22-bit operands)
-REPORT = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "gpurun_out", "parity_report.jsonl")
+REPORT = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "reports", "parity_report.jsonl")   # git-ignored
 
 
 def _report(**kw):

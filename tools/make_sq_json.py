@@ -1,5 +1,5 @@
 """profiles/<round>_sq_summary.json from one SQ-counter pass (tools/rocpd_pmc.py --json of `rocprofv3 --pmc SQ_WAVE_CYCLES SQ_WAIT_ANY SQ_WAIT_INST_ANY
-SQ_ACTIVE_INST_ANY SQ_VALU_MFMA_BUSY_CYCLES SQ_LDS_BANK_CONFLICT SQ_LDS_IDX_ACTIVE SQ_BUSY_CYCLES GRBM_GUI_ACTIVE -- python bench.py --eager ...`):
+SQ_ACTIVE_INST_ANY SQ_VALU_MFMA_BUSY_CYCLES SQ_LDS_BANK_CONFLICT SQ_LDS_IDX_ACTIVE SQ_BUSY_CYCLES GRBM_GUI_ACTIVE -- python bench.py --full --eager ...`):
 per kernel, the fractions tools/sq_fractions.py prints.  bench.py attaches the dominant kernel's entry to `roofline.sq_counters`.
 
     python tools/make_sq_json.py gpurun_out/r04j_pmc_sq.json profiles/r04_sq_summary.json "profiles/r04j_pmc_sq.json" """
