@@ -30,8 +30,10 @@ const char* psalm_last_error(void);
  * 6: psalm_gemm_x3_set_products, psalm_fuse_masks, the stage-level psalm_phi_forward (r05); psalm_causal_attention_f32_workspace grew by one
  *    byte per 32-key tile.
  * 7: psalm_set_tuning / psalm_get_tuning, psalm_layernorm_chain, psalm_gemm_f32_pair, psalm_postprocess*, psalm_predictor_kv + the kv_ready argument of
- *    psalm_predictor_forward (r06). */
-#define PSALM_ABI_VERSION 7
+ *    psalm_predictor_forward (r06).
+ * 8: image sessions: psalm_causal_attention_f32_prefix[_split] (+ _workspace), psalm_phi_prefix_kv_store, the stage-level psalm_phi_prefix /
+ *    psalm_phi_suffix (+ their _workspace / _cache_bytes functions). */
+#define PSALM_ABI_VERSION 8
 int psalm_abi_version(void);
 const char* psalm_backend(void); /* "hip-gfx950" */
 
@@ -236,6 +238,34 @@ int psalm_causal_attention_f32_split(const float* qkv, long ld, int q_off, int k
                                      const unsigned char* key_mask, void* workspace, int B, int L, int heads, int head_dim, int rot,
                                      void* stream);
 
+/* Prefix form of the Phi attention (image sessions: one image, N prompts that share their first P rows -- system text + image tokens).  The
+ * sequence of prompt n is [P prefix rows | S suffix rows]; only the N * S suffix rows carry queries.  Suffix query s of prompt n attends the P
+ * prefix keys (all real, never masked) and the suffix keys s' <= s of its own prompt with key_mask[n, s'] = 1 (modeling_phi.py:189-245 on the
+ * concatenated sequence); softmax statistics are merged online across the prefix / suffix boundary.
+ *   qkv            the suffix [k | v | q | ...] buffer, N * S rows of ld floats, column offsets as psalm_causal_attention_f32
+ *   k_cache        RoPE'd prefix K of this layer, (heads, ceil32(P), 64) fp32, rows >= P zero (psalm_phi_prefix_kv_store writes it; the layout is
+ *                  the one the prefill's RoPE pre-pass leaves in its workspace); shared by all N prompts
+ *   v_cache        prefix V, P rows of ldv >= heads * 64 floats (head h at columns h * 64 ..)
+ *   cos / sin      the (>= P + S, rot) tables; suffix row s uses row P + s
+ *   key_mask       (N, S) u8 over the suffix keys
+ * Any P >= 1, S >= 1.  Rows of fully padded prompts' tails receive finite values.  Workspace: psalm_causal_attention_f32_prefix_workspace(N, S,
+ * heads) bytes, 16-byte aligned.  The _split entry writes split-f16 operand columns under caller-given row scales exactly as
+ * psalm_causal_attention_f32_split does.  P * ldv * 4 and S * ld * 4 must stay below 2 GiB. */
+long psalm_causal_attention_f32_prefix_workspace(int N, int S, int heads);
+int psalm_causal_attention_f32_prefix(const float* qkv, long ld, int q_off, int k_off, int v_off, const float* k_cache, const float* v_cache,
+                                      long ldv, float* out, long ldo, int o_off, const float* cos_table, const float* sin_table,
+                                      const unsigned char* key_mask, void* workspace, int N, int S, int P, int heads, int head_dim, int rot,
+                                      void* stream);
+int psalm_causal_attention_f32_prefix_split(const float* qkv, long ld, int q_off, int k_off, int v_off, const float* k_cache,
+                                            const float* v_cache, long ldv, void* split_out, long ld_split, int split_kp, int split_col_off,
+                                            const float* split_inv, const float* cos_table, const float* sin_table,
+                                            const unsigned char* key_mask, void* workspace, int N, int S, int P, int heads, int head_dim,
+                                            int rot, void* stream);
+/* Producer of one layer's prefix cache from the [k | v | q | ...] buffer of the P prefix rows (positions 0 .. P-1): k_cache <- RoPE(k) in the
+ * (heads, ceil32(P), 64) layout (padding rows zero), v_cache row t <- v of row t (row stride ldv floats). */
+int psalm_phi_prefix_kv_store(const float* qkv, long ld, int k_off, int v_off, const float* cos_table, const float* sin_table, float* k_cache,
+                              float* v_cache, long ldv, int P, int heads, int head_dim, int rot, void* stream);
+
 /* zero `bytes` bytes / copy `bytes` bytes device-to-device, as stream operations (hipMemsetAsync / hipMemcpyAsync; graph-capturable) */
 int psalm_memset_zero(void* p, long bytes, void* stream);
 int psalm_copy_d2d(void* dst, const void* src, long bytes, void* stream);
@@ -435,6 +465,32 @@ long psalm_phi_forward_workspace(const psalm_phi_desc* d, int B, int L);
 int psalm_phi_forward(const psalm_phi_desc* d, const float* embeds, const unsigned char* key_mask, const float* cos_table, const float* sin_table,
                       int B, int L, float* hidden_out, void* workspace, long workspace_bytes, void* gemm_workspace, long gemm_workspace_bytes,
                       void* stream);
+
+/* Image sessions (PSALM.encode_image / PSALM.segment): the Phi pass split at the end of the prompt-independent prefix, precision "f16x3".
+ * psalm_phi_prefix: the layer sequence of psalm_phi_forward on the P prefix rows (embeds (P, hidden), positions 0 .. P-1, key_mask (P) u8 all
+ *   ones); each layer's RoPE'd K and its V go into the caller-owned `cache` of psalm_phi_prefix_cache_bytes(d, P) bytes (256-byte aligned; per
+ *   layer: K (heads, ceil32(P), 64) f32, then V (P, hidden) f32, each padded to 256 bytes).  The last layer stops behind its [k|v|q|fc1] GEMM.
+ * psalm_phi_suffix: per layer the [k|v|q|fc1] GEMM on the N * S suffix rows, psalm_causal_attention_f32_prefix_split against that layer's
+ *   cache, [dense|fc2] + residual + the next LayerNorm -- the op-level entries and fusions of psalm_phi_forward.  embeds (N*S, hidden), key_mask
+ *   (N, S) u8, cos / sin (>= P + S, rot), hidden_out (N*S, hidden) = final LayerNorm output.
+ * Workspaces: psalm_phi_prefix_workspace(d, P) / psalm_phi_suffix_workspace(d, N, S) bytes, 256-byte aligned.
+ * Scale contract of the suffix pass: the attention columns of the [dense|fc2] operand leave under the row scales psalm_gemm_x3_split derives with
+ *   global_rows = 1, i.e. from max_r a_scale[r] over the rows of THAT call -- the N * S suffix rows.  The attention output also averages the cached
+ *   prefix V rows, which that maximum does not see: the bound covers them only while the prefix rows' largest LayerNorm-output scale is not above
+ *   the suffix rows' largest.  It is not enforced; what stands behind it is the slack of the format -- bound * scale < 2^13 against f16's 2^16, so
+ *   a prefix row would need a scale more than 8 x every suffix row's AND a V entry at the L1-norm bound to overflow (DESIGN.md section 0*). */
+long psalm_phi_prefix_cache_bytes(const psalm_phi_desc* d, int P);
+/* One layer's share of that cache for a model without a descriptor at hand: returns its bytes, *k_bytes = where its V block starts, *v_bytes
+ * = the V block's bytes (either may be null).  psalm_phi_prefix_cache_bytes(d, P) = num_layers times the returned value. */
+long psalm_phi_prefix_cache_layer_bytes(int hidden, int heads, int P, long* k_bytes, long* v_bytes);
+long psalm_phi_prefix_workspace(const psalm_phi_desc* d, int P);
+int psalm_phi_prefix(const psalm_phi_desc* d, const float* embeds, const unsigned char* key_mask, const float* cos_table, const float* sin_table,
+                     int P, void* cache, long cache_bytes, void* workspace, long workspace_bytes, void* gemm_workspace,
+                     long gemm_workspace_bytes, void* stream);
+long psalm_phi_suffix_workspace(const psalm_phi_desc* d, int N, int S);
+int psalm_phi_suffix(const psalm_phi_desc* d, const float* embeds, const unsigned char* key_mask, const float* cos_table, const float* sin_table,
+                     int N, int S, int P, const void* cache, long cache_bytes, float* hidden_out, void* workspace, long workspace_bytes,
+                     void* gemm_workspace, long gemm_workspace_bytes, void* stream);
 
 /* psalm_swin_forward: SwinTransformer.forward (swin_trans.py:608-633; blocks :194-253, window attention :117-149, patch merging :266-296, patch
  * embedding :427-443), precision "f16x3", 12 x 12 windows, head dim 32.  GEMM weights in split-f16 form (`*_w` rows of 2*ceil64(K) f16, `*_ws`

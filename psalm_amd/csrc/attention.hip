@@ -991,6 +991,302 @@ extern "C" int psalm_causal_attention_f32_split(const float* qkv, long ld, int q
                                      B, L, heads, head_dim, rot, stream, split_inv, split_kp, "psalm_causal_attention_f32_split");
 }
 
+// ---- prefix form (image sessions: one image, many prompts).  The sequence of every prompt is [prefix of P rows | suffix of S rows]; the prefix --
+// system text + image tokens -- is the same for all N prompts, so its RoPE'd K and its V were computed ONCE per layer (psalm_phi_prefix_kv_store)
+// and only the N * S suffix rows carry queries.  Suffix query s of prompt n sees the P prefix keys (all real) and the suffix keys s' <= s of its
+// own prompt with key_mask[n, s'] = 1.
+// Blocking: a block owns ONE 32-query tile of one (prompt, head); its 4 wavefronts are dealt the key tiles of the CONCATENATED list
+// [prefix tiles 0 .. Pp/32-1 | suffix tiles 0 .. qt] round-robin, each with a private online-softmax state, merged through LDS exactly as
+// in causal_attention_f32_splitk_kernel (the merge is what carries the softmax across the prefix / suffix boundary).  Query tiles are NOT paired:
+// pairing balances the graded causal work of a long prefill (29 tiles), but here every tile walks the same Pp/32 prefix tiles first and the
+// causal part (S of 130 .. 260: at most 9 tiles) is the small term; with N = 1 the grid is heads x ceil(S/32) = 160 .. 288 blocks, about one per
+// CU, and pairing would halve it.  Heaviest query tile first.  Fragment fetches through buffer descriptors (rows >= P of the V cache, >= S of the
+// suffix V read as zeros, their probabilities are zeros as well); the K cache is zero-padded to Pp rows by its producer.
+__global__ void __launch_bounds__(256) phi_prefix_kv_store_kernel(const float* __restrict__ base, long ld, int k_off, int v_off,
+                                                                  const float* __restrict__ cosT, const float* __restrict__ sinT,
+                                                                  float* __restrict__ Kc, float* __restrict__ Vc, long ldv, int P, int Pp, int heads) {
+    constexpr int HD = 64, ROT = 32, half = 16;
+    const int h = blockIdx.y;
+    const int t = blockIdx.x * 32 + (threadIdx.x >> 3), c0 = (threadIdx.x & 7) * 8;     // token, 8-wide head-dim chunk (as phi_rope_prep_f32_kernel)
+    if (t >= Pp) return;
+    float* kd = Kc + ((long)h * Pp + t) * HD + c0;
+    float k[8];
+    if (t < P) {
+        const float* p = base + (long)t * ld;
+        ld8(p + k_off + h * HD + c0, k);
+        if (c0 < ROT) {
+            float ko[8], cs[8], sn[8];
+            const int oc = c0 < half ? c0 + half : c0 - half;
+            ld8(p + k_off + h * HD + oc, ko);
+            ld8(cosT + (long)t * ROT + c0, cs);
+            ld8(sinT + (long)t * ROT + c0, sn);
+#pragma unroll
+            for (int i = 0; i < 8; ++i) k[i] = k[i] * cs[i] + (c0 < half ? -ko[i] : ko[i]) * sn[i];
+        }
+        float v[8];
+        ld8(p + v_off + h * HD + c0, v);
+        st8(Vc + (long)t * ldv + h * HD + c0, v);
+    } else {
+#pragma unroll
+        for (int i = 0; i < 8; ++i) k[i] = 0.f;
+    }
+    st8(kd, k);
+}
+
+extern "C" int psalm_phi_prefix_kv_store(const float* qkv, long ld, int k_off, int v_off, const float* cos_table, const float* sin_table,
+                                         float* k_cache, float* v_cache, long ldv, int P, int heads, int head_dim, int rot, void* stream) {
+    PSALM_CHECK_ARG(head_dim == 64 && rot == 32, "psalm_phi_prefix_kv_store: head_dim 64, rotary dim 32 (Phi-1.5)");
+    PSALM_CHECK_ARG(qkv && cos_table && sin_table && k_cache && v_cache && P >= 1 && heads >= 1, "psalm_phi_prefix_kv_store: null argument / empty prefix");
+    PSALM_CHECK_ARG(ld % 4 == 0 && k_off % 4 == 0 && v_off % 4 == 0 && ldv % 4 == 0 && ldv >= (long)heads * 64 && (uintptr_t)qkv % 16 == 0 &&
+                        (uintptr_t)k_cache % 16 == 0 && (uintptr_t)v_cache % 16 == 0,
+                    "psalm_phi_prefix_kv_store: 16-byte aligned rows / offsets, v_cache rows of >= heads * 64 floats");
+    const int Pp = (P + 31) / 32 * 32;
+    hipLaunchKernelGGL(phi_prefix_kv_store_kernel, dim3(Pp / 32, heads), dim3(256), 0, (hipStream_t)stream, qkv, ld, k_off, v_off, cos_table,
+                       sin_table, k_cache, v_cache, ldv, P, Pp, heads);
+    PSALM_LAUNCH_END("psalm_phi_prefix_kv_store");
+}
+
+template <bool SO>
+__global__ void __launch_bounds__(256) PSALM_WAVES_PER_EU(3)
+causal_attention_f32_prefix_kernel(const float* __restrict__ Qr, const float* __restrict__ Kr, const unsigned char* __restrict__ Mk,
+                                   const unsigned char* __restrict__ Tk, const float* __restrict__ base, long ld, int v_off,
+                                   const float* __restrict__ Kc, const float* __restrict__ Vc, long ldv, int P, int Pp, float* out, long ldo,
+                                   int o_off, int S, int Sp, int heads, const float* __restrict__ so_inv, int so_kp, int xcd_heads) {
+    typedef float f32x16 __attribute__((ext_vector_type(16)));
+    constexpr int HD = 64, OS = HD + 4;
+    __shared__ __attribute__((aligned(16))) float Os[4][32 * OS];         // per-wave O (q-major) for the merge
+    __shared__ float Ml[4][2][32];                                        // per-wave (m, l) per query
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, n32 = lane & 31, hi = lane >> 5;
+    const int nqt = Sp / 32, npt = Pp / 32;
+    int bx = blockIdx.x, h = blockIdx.y, b = blockIdx.z;                   // XCD x runs the (prompt, head) pairs x, x + 8, ...: see causal_attention_f32_splitk_kernel
+    if (xcd_heads) {
+        const int lin = (int)(blockIdx.x + gridDim.x * (blockIdx.y + gridDim.y * blockIdx.z));
+        const int j = lin >> 3, hb = (lin & 7) + 8 * (j / (int)gridDim.x);
+        bx = j % (int)gridDim.x;
+        h = hb % heads;
+        b = hb / heads;
+    }
+    const long bh = (long)b * heads + h;
+    const int qt = nqt - 1 - bx;                                          // heaviest (last) query tile first
+    const int qi = qt * 32 + n32;                                         // this lane's query column (row qi < Sp of Qr)
+    float qv[32];
+    {
+        const float* p = Qr + (bh * Sp + qi) * HD + 32 * hi;
+#pragma unroll
+        for (int c = 0; c < 32; c += 4) {
+            const psalm_f32x4 t = *reinterpret_cast<const psalm_f32x4*>(p + c);
+            qv[c] = t.x; qv[c + 1] = t.y; qv[c + 2] = t.z; qv[c + 3] = t.w;
+        }
+    }
+    f32x16 o0, o1;
+#pragma unroll
+    for (int r = 0; r < 16; ++r) { o0[r] = 0.f; o1[r] = 0.f; }
+    float m = -3.0e38f, l = 0.f;
+    // one 32-key tile: K rows kt*32.. of `krs` ((rows, 64) fp32), V rows of `vrs` (row stride vrow bytes).  pre: a prefix tile -- keys < P are
+    // visible to every query; else a suffix tile -- causal + key mask (Mk / Tk of the pre-pass).
+    auto tile = [&](const bool pre, const psalm_rsrc krs, const psalm_rsrc vrs, const unsigned vvo, const unsigned vrow, const int kt) {
+        const unsigned kvo = (unsigned)((n32 * HD + 32 * hi) * 4);
+        psalm_f32x4 kf[8];
+#pragma unroll
+        for (int c = 0; c < 8; ++c) {
+            const psalm_u32x4 t = psalm_buf_load_b128_s(krs, kvo + 16u * c, (unsigned)(kt * 32 * HD * 4));
+            kf[c] = psalm_f32x4{__builtin_bit_cast(float, t.x), __builtin_bit_cast(float, t.y), __builtin_bit_cast(float, t.z), __builtin_bit_cast(float, t.w)};
+        }
+        float va[16], vb[16];                                             // V^T fragments: step r = 4g + i contracts key 8g + 4hi + i
+#pragma unroll
+        for (int g = 0; g < 4; ++g)
+#pragma unroll
+            for (int i = 0; i < 4; ++i) {
+                const unsigned so_ = (unsigned)(kt * 32 + 8 * g + i) * vrow;
+                va[4 * g + i] = psalm_buf_load_f32_s(vrs, vvo, so_);
+                vb[4 * g + i] = psalm_buf_load_f32_s(vrs, vvo + 128u, so_);
+            }
+        const bool plain = pre ? (kt * 32 + 32 <= P)
+                               : (__builtin_amdgcn_readfirstlane((int)(kt < qt && Tk[(long)b * nqt + kt] != 0)) != 0);       // (wave-uniform)
+        f32x16 sacc;
+#pragma unroll
+        for (int r = 0; r < 16; ++r) sacc[r] = 0.f;
+#pragma unroll
+        for (int c = 0; c < 8; ++c) {
+            sacc = __builtin_amdgcn_mfma_f32_32x32x2f32(kf[c].x, qv[4 * c], sacc, 0, 0, 0);
+            sacc = __builtin_amdgcn_mfma_f32_32x32x2f32(kf[c].y, qv[4 * c + 1], sacc, 0, 0, 0);
+            sacc = __builtin_amdgcn_mfma_f32_32x32x2f32(kf[c].z, qv[4 * c + 2], sacc, 0, 0, 0);
+            sacc = __builtin_amdgcn_mfma_f32_32x32x2f32(kf[c].w, qv[4 * c + 3], sacc, 0, 0, 0);
+        }
+        float mc = -3.0e38f, mn, alpha, psum = 0.f;
+        if (plain) {
+#pragma unroll
+            for (int r = 0; r < 16; ++r) mc = fmaxf(mc, sacc[r]);
+            mc = fmaxf(mc, __shfl_xor(mc, 32));
+            mn = fmaxf(m, mc);
+            alpha = __expf(m - mn);
+#pragma unroll
+            for (int r = 0; r < 16; ++r) {
+                const float p = __expf(sacc[r] - mn);
+                sacc[r] = p;
+                psum += p;
+            }
+        } else {
+            unsigned mw[4] = {0x01010101u, 0x01010101u, 0x01010101u, 0x01010101u};      // key-valid bytes of keys 8g + 4hi .. +3
+            if (!pre) {
+#pragma unroll
+                for (int g = 0; g < 4; ++g) mw[g] = *reinterpret_cast<const unsigned*>(Mk + (long)b * Sp + kt * 32 + 8 * g + 4 * hi);
+            }
+#pragma unroll
+            for (int r = 0; r < 16; ++r) {
+                const int j = (r & 3) + 8 * (r >> 2) + 4 * hi;
+                const bool ok = (pre ? (kt * 32 + j < P) : (kt * 32 + j <= qi)) && ((mw[r >> 2] >> (8 * (r & 3))) & 0xffu);
+                sacc[r] = ok ? sacc[r] : -3.0e38f;
+                mc = fmaxf(mc, sacc[r]);
+            }
+            mc = fmaxf(mc, __shfl_xor(mc, 32));
+            mn = fmaxf(m, mc);
+            alpha = __expf(m - mn);
+#pragma unroll
+            for (int r = 0; r < 16; ++r) {
+                const float p = sacc[r] > -1.0e38f ? __expf(sacc[r] - mn) : 0.f;
+                sacc[r] = p;
+                psum += p;
+            }
+        }
+        psum += __shfl_xor(psum, 32);
+        l = l * alpha + psum;
+        m = mn;
+#pragma unroll
+        for (int r = 0; r < 16; ++r) { o0[r] *= alpha; o1[r] *= alpha; }
+#pragma unroll
+        for (int r = 0; r < 16; ++r) {
+            o0 = __builtin_amdgcn_mfma_f32_32x32x2f32(va[r], sacc[r], o0, 0, 0, 0);
+            o1 = __builtin_amdgcn_mfma_f32_32x32x2f32(vb[r], sacc[r], o1, 0, 0, 0);
+        }
+    };
+    {
+        // prefix tiles: wave w takes the tiles w, w + 4, ... of the concatenated list, which continues into the suffix below
+        const psalm_rsrc vrs = psalm_make_rsrc(Vc + h * HD, (unsigned)((((long)P - 1) * ldv + HD) * 4));
+        const psalm_rsrc krs = psalm_make_rsrc(Kc + (long)h * Pp * HD, (unsigned)((long)Pp * HD * 4));
+        const unsigned vvo = (unsigned)((4L * hi * ldv + n32) * 4);
+        for (int kt = __builtin_amdgcn_readfirstlane(wave); kt < npt; kt += 4) tile(true, krs, vrs, vvo, (unsigned)(ldv * 4), kt);
+    }
+    {
+        const psalm_rsrc vrs = psalm_make_rsrc(base + (long)b * S * ld + v_off + h * HD, (unsigned)((((long)S - 1) * ld + HD) * 4));
+        const psalm_rsrc krs = psalm_make_rsrc(Kr + bh * Sp * HD, (unsigned)((long)Sp * HD * 4));
+        const unsigned vvo = (unsigned)((4L * hi * ld + n32) * 4);
+        const int first = (wave + 4 - (npt & 3)) & 3;                     // list index npt + kt belongs to wave (npt + kt) % 4
+        for (int kt = __builtin_amdgcn_readfirstlane(first); kt <= qt; kt += 4) tile(false, krs, vrs, vvo, (unsigned)(ld * 4), kt);
+    }
+    // ---- merge the 4 key-interleaved states: O = sum_w O_w e^(m_w - M) / sum_w l_w e^(m_w - M)
+    {
+        float* ow = &Os[wave][n32 * OS + 4 * hi];
+#pragma unroll
+        for (int g = 0; g < 4; ++g) {                                    // rows d = 8g + 4hi + {0..3} (+32 for the second d-tile)
+            *reinterpret_cast<psalm_f32x4*>(ow + 8 * g) = psalm_f32x4{o0[4 * g], o0[4 * g + 1], o0[4 * g + 2], o0[4 * g + 3]};
+            *reinterpret_cast<psalm_f32x4*>(ow + 32 + 8 * g) = psalm_f32x4{o1[4 * g], o1[4 * g + 1], o1[4 * g + 2], o1[4 * g + 3]};
+        }
+        if (hi == 0) { Ml[wave][0][n32] = m; Ml[wave][1][n32] = l; }
+    }
+    __syncthreads();
+    {
+        const int q = tid >> 3, d0 = (tid & 7) * 8;                       // thread -> query q of the tile, 8 head dims
+        const int tq = qt * 32 + q;
+        if (tq < S) {
+            float M = -3.0e38f;
+#pragma unroll
+            for (int w = 0; w < 4; ++w) M = fmaxf(M, Ml[w][0][q]);
+            float Lsum = 0.f, acc[8] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+            for (int w = 0; w < 4; ++w) {
+                const float mw_ = Ml[w][0][q];
+                const float f = mw_ > -1.0e38f ? __expf(mw_ - M) : 0.f;
+                Lsum += Ml[w][1][q] * f;
+                const psalm_f32x4 a = *reinterpret_cast<const psalm_f32x4*>(&Os[w][q * OS + d0]);
+                const psalm_f32x4 c = *reinterpret_cast<const psalm_f32x4*>(&Os[w][q * OS + d0 + 4]);
+                acc[0] += a.x * f; acc[1] += a.y * f; acc[2] += a.z * f; acc[3] += a.w * f;
+                acc[4] += c.x * f; acc[5] += c.y * f; acc[6] += c.z * f; acc[7] += c.w * f;
+            }
+            const float inv = Lsum > 0.f ? 1.f / Lsum : 0.f;
+#pragma unroll
+            for (int i = 0; i < 8; ++i) acc[i] *= inv;
+            const long row = (long)b * S + tq;
+            if constexpr (SO) {
+                const float sc = 1.f / so_inv[row];                      // power of two: exact
+                unsigned hw[4], lw[4];
+#pragma unroll
+                for (int k = 0; k < 4; ++k) {
+                    unsigned h0, h1, l0, l1;
+                    psalm_split_words(acc[2 * k] * sc, h0, l0);
+                    psalm_split_words(acc[2 * k + 1] * sc, h1, l1);
+                    hw[k] = h0 | (h1 << 16);
+                    lw[k] = l0 | (l1 << 16);
+                }
+                unsigned short* d = reinterpret_cast<unsigned short*>(out) + row * ldo + o_off + h * HD + d0;
+                *reinterpret_cast<psalm_u32x4*>(d) = psalm_u32x4{hw[0], hw[1], hw[2], hw[3]};
+                *reinterpret_cast<psalm_u32x4*>(d + so_kp) = psalm_u32x4{lw[0], lw[1], lw[2], lw[3]};
+            } else {
+                st8(out + row * ldo + o_off + h * HD + d0, acc);
+            }
+        }
+    }
+}
+
+extern "C" long psalm_causal_attention_f32_prefix_workspace(int N, int S, int heads) {
+    return psalm_causal_attention_f32_workspace(N, S, heads);              // RoPE'd Q / K of the suffix rows + their padded key mask
+}
+
+static int causal_attention_f32_prefix_impl(const float* qkv, long ld, int q_off, int k_off, int v_off, const float* k_cache, const float* v_cache,
+                                            long ldv, void* out, long ldo, int o_off, const float* cos_table, const float* sin_table,
+                                            const unsigned char* key_mask, void* workspace, int N, int S, int P, int heads, int head_dim, int rot,
+                                            void* stream, const float* so_inv, int so_kp, const char* name) {
+    PSALM_CHECK_ARG(head_dim == 64 && rot == 32, "psalm_causal_attention_f32_prefix: head_dim 64, rotary dim 32 (Phi-1.5)");
+    PSALM_CHECK_ARG(ld % 4 == 0 && q_off % 4 == 0 && k_off % 4 == 0 && v_off % 4 == 0 && (uintptr_t)qkv % 16 == 0 &&
+                        (uintptr_t)out % 16 == 0 && workspace && (uintptr_t)workspace % 16 == 0 &&
+                        (so_inv ? (ldo % 8 == 0 && o_off % 8 == 0 && so_kp % 8 == 0) : (ldo % 4 == 0 && o_off % 4 == 0)),
+                    "psalm_causal_attention_f32_prefix: 16-byte aligned rows / offsets and a workspace");
+    PSALM_CHECK_ARG(P >= 1 && k_cache && v_cache && (uintptr_t)k_cache % 16 == 0 && (uintptr_t)v_cache % 16 == 0 && ldv % 4 == 0 &&
+                        ldv >= (long)heads * 64 && key_mask && cos_table && sin_table,
+                    "psalm_causal_attention_f32_prefix: a prefix of >= 1 rows: K cache (heads, ceil32(P), 64), V cache rows of >= heads * 64 floats, 16-byte aligned");
+    if (N == 0 || S == 0) return 0;
+    const int Sp = (S + 31) / 32 * 32, Pp = (P + 31) / 32 * 32;
+    PSALM_CHECK_ARG(((long)S - 1) * ld * 4 + 256 < 0x7fffffffL && ((long)P - 1) * ldv * 4 + 256 < 0x7fffffffL && (long)Pp * 64 * 4 < 0x7fffffffL,
+                    "psalm_causal_attention_f32_prefix: S * ld * 4 and P * ldv * 4 must stay below 2 GiB (buffer-descriptor fetches)");
+    float* Qr = (float*)workspace;
+    float* Kr = Qr + (long)N * heads * Sp * 64;
+    unsigned char* Mk = (unsigned char*)(Kr + (long)N * heads * Sp * 64);
+    unsigned char* Tk = Mk + (long)N * Sp;
+    const float scale = 1.0f / sqrtf((float)head_dim);
+    hipStream_t s = (hipStream_t)stream;
+    // the suffix rows sit at the absolute positions P + s: the same pre-pass as the prefill's, on tables that start at row P
+    hipLaunchKernelGGL(phi_rope_prep_f32_kernel, dim3(Sp / 32, heads, N), dim3(256), 0, s, qkv, ld, q_off, k_off, cos_table + (long)P * rot,
+                       sin_table + (long)P * rot, key_mask, Qr, Kr, Mk, Tk, S, Sp, heads, scale);
+    const dim3 grid(Sp / 32, heads, N);
+    const int xcd_heads = ((heads * N) % 8 == 0 && psalm_get_tuning(PSALM_TUNE_ATTN_XCD_HEADS)) ? 1 : 0;
+    if (so_inv)
+        hipLaunchKernelGGL(causal_attention_f32_prefix_kernel<true>, grid, dim3(256), 0, s, (const float*)Qr, (const float*)Kr, (const unsigned char*)Mk,
+                           (const unsigned char*)Tk, qkv, ld, v_off, k_cache, v_cache, ldv, P, Pp, (float*)out, ldo, o_off, S, Sp, heads, so_inv, so_kp, xcd_heads);
+    else
+        hipLaunchKernelGGL(causal_attention_f32_prefix_kernel<false>, grid, dim3(256), 0, s, (const float*)Qr, (const float*)Kr, (const unsigned char*)Mk,
+                           (const unsigned char*)Tk, qkv, ld, v_off, k_cache, v_cache, ldv, P, Pp, (float*)out, ldo, o_off, S, Sp, heads,
+                           (const float*)nullptr, 0, xcd_heads);
+    PSALM_LAUNCH_END(name);
+}
+extern "C" int psalm_causal_attention_f32_prefix(const float* qkv, long ld, int q_off, int k_off, int v_off, const float* k_cache,
+                                                 const float* v_cache, long ldv, float* out, long ldo, int o_off, const float* cos_table,
+                                                 const float* sin_table, const unsigned char* key_mask, void* workspace, int N, int S, int P,
+                                                 int heads, int head_dim, int rot, void* stream) {
+    return causal_attention_f32_prefix_impl(qkv, ld, q_off, k_off, v_off, k_cache, v_cache, ldv, out, ldo, o_off, cos_table, sin_table, key_mask,
+                                            workspace, N, S, P, heads, head_dim, rot, stream, nullptr, 0, "psalm_causal_attention_f32_prefix");
+}
+extern "C" int psalm_causal_attention_f32_prefix_split(const float* qkv, long ld, int q_off, int k_off, int v_off, const float* k_cache,
+                                                       const float* v_cache, long ldv, void* split_out, long ld_split, int split_kp,
+                                                       int split_col_off, const float* split_inv, const float* cos_table, const float* sin_table,
+                                                       const unsigned char* key_mask, void* workspace, int N, int S, int P, int heads,
+                                                       int head_dim, int rot, void* stream) {
+    PSALM_CHECK_ARG(split_out && split_inv && ld_split >= 2L * split_kp && split_col_off + heads * 64 <= split_kp,
+                    "psalm_causal_attention_f32_prefix_split: split buffer rows of >= 2*split_kp f16 and the row scales");
+    return causal_attention_f32_prefix_impl(qkv, ld, q_off, k_off, v_off, k_cache, v_cache, ldv, split_out, ld_split, split_col_off, cos_table,
+                                            sin_table, key_mask, workspace, N, S, P, heads, head_dim, rot, stream, split_inv, split_kp,
+                                            "psalm_causal_attention_f32_prefix_split");
+}
+
 extern "C" int psalm_causal_attention(const void* qkv, int dtype, long ld, int q_off, int k_off, int v_off, void* out, long ldo,
                                       int o_off, const float* cos_table, const float* sin_table,
                                       const unsigned char* key_mask, int B, int L, int heads, int head_dim, int rot,

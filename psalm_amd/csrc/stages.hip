@@ -108,8 +108,131 @@ extern "C" int psalm_phi_forward(const psalm_phi_desc* d, const float* embeds, c
     return 0;
 }
 
+// ================================================================================================= image sessions: Phi prefix / suffix passes
+//   psalm_phi_prefix / psalm_phi_suffix: psalm_phi_forward cut at the end of the prompt-independent prefix (system text + image tokens).  Attention is
+//   causal, so the prefix rows' K / V are those of the one-shot pass whatever follows them: the prefix pass (once per image) leaves each layer's RoPE'd
+//   K and its V in the caller's cache, the suffix pass (once per call, N prompts) runs the same GEMMs / fusions on the N * S suffix rows and the prefix
+//   attention kernel against the cache.  The op-by-op Python form is PSALM._llm_session (tests/test_11_session_emu.py: same bits).
+struct PhiCacheLayout { long k_bytes, v_bytes, stride; int Pp; };
+static PhiCacheLayout phi_cache_layout(int hidden, int heads, int P) {
+    PhiCacheLayout c;
+    c.Pp = (P + 31) / 32 * 32;
+    c.k_bytes = al256((long)heads * c.Pp * 64 * 4);
+    c.v_bytes = al256((long)P * hidden * 4);
+    c.stride = c.k_bytes + c.v_bytes;
+    return c;
+}
+static PhiCacheLayout phi_cache_layout(const psalm_phi_desc* d, int P) { return phi_cache_layout(d->hidden, d->heads, P); }
+
+extern "C" long psalm_phi_prefix_cache_layer_bytes(int hidden, int heads, int P, long* k_bytes, long* v_bytes) {
+    if (hidden <= 0 || heads <= 0 || P <= 0) return -1;
+    const PhiCacheLayout c = phi_cache_layout(hidden, heads, P);
+    if (k_bytes) *k_bytes = c.k_bytes;
+    if (v_bytes) *v_bytes = c.v_bytes;
+    return c.stride;
+}
+
+extern "C" long psalm_phi_prefix_cache_bytes(const psalm_phi_desc* d, int P) {
+    if (phi_check(d) != 0 || P <= 0) return -1;
+    return phi_cache_layout(d, P).stride * d->num_layers;
+}
+extern "C" long psalm_phi_prefix_workspace(const psalm_phi_desc* d, int P) {
+    if (phi_check(d) != 0 || P <= 0) return -1;
+    return phi_layout(d, 1, P).total;
+}
+extern "C" long psalm_phi_suffix_workspace(const psalm_phi_desc* d, int N, int S) {
+    if (phi_check(d) != 0 || N <= 0 || S <= 0) return -1;
+    return phi_layout(d, N, S).total;
+}
+
+// suffix = false: the P = L prefix rows (B = 1), cache written; suffix = true: B * L suffix rows behind a prefix of P rows, cache read
+static int phi_session_pass(const psalm_phi_desc* d, bool suffix, const float* embeds, const unsigned char* key_mask, const float* cos_table,
+                            const float* sin_table, int B, int L, int P, char* cache, long cache_bytes, float* hidden_out, void* workspace,
+                            long workspace_bytes, void* gemm_workspace, long gemm_workspace_bytes, void* stream) {
+    const PhiLayout lo = phi_layout(d, B, L);
+    const PhiCacheLayout cl = phi_cache_layout(d, P);
+    PSALM_CHECK_ARG(workspace_bytes >= lo.total && (uintptr_t)workspace % 256 == 0, "psalm_phi_prefix / _suffix: workspace of the _workspace() function's bytes, 256-byte aligned");
+    PSALM_CHECK_ARG(cache_bytes >= cl.stride * d->num_layers && (uintptr_t)cache % 256 == 0, "psalm_phi_prefix / _suffix: cache of psalm_phi_prefix_cache_bytes() bytes, 256-byte aligned");
+    char* ws = (char*)workspace;
+    const int M = B * L, H = d->hidden, I = d->intermediate, Kp = lo.Kp, K2 = H + I;
+    float* x[2] = {(float*)(ws + lo.x0), (float*)(ws + lo.x1)};
+    void* h = ws + lo.h;
+    float* hinv = (float*)(ws + lo.hinv);
+    float* big = (float*)(ws + lo.big);
+    void* a2 = ws + lo.a2;
+    float* inv2 = (float*)(ws + lo.inv2);
+    void* attn = ws + lo.attn;
+    int rc;
+    const psalm_phi_layer* l0 = &d->layers[0];
+    rc = psalm_layernorm_split(embeds, H, nullptr, H, l0->ln_g, l0->ln_b, M, H, d->ln_eps, h, hinv, nullptr, 0, nullptr, nullptr, stream);
+    if (rc) return rc;
+    const float* xin = embeds;
+    int cur = 0;
+    for (int i = 0; i < d->num_layers; ++i) {
+        const psalm_phi_layer* ly = &d->layers[i];
+        const bool last = i == d->num_layers - 1;
+        PSALM_CHECK_ARG(ly->w1 && ly->w1_scale && ly->b1 && ly->w2 && ly->w2_scale && ly->b2 && ly->bnd, "psalm_phi_prefix / _suffix: layer weights missing");
+        float* kc = (float*)(cache + cl.stride * i);
+        float* vc = (float*)(cache + cl.stride * i + cl.k_bytes);
+        rc = psalm_gemm_x3_split(h, 2L * Kp, hinv, ly->w1, 2L * Kp, ly->w1_scale, Kp, ly->b1, big, 3L * H, M, 3 * H + I, /*gelu_new*/ 3, 3 * H, a2,
+                                 2L * K2, K2, H, 3 * H, ly->paired, inv2, ly->bnd, 1, gemm_workspace, gemm_workspace_bytes, stream);
+        if (rc) return rc;
+        if (!suffix) {
+            rc = psalm_phi_prefix_kv_store(big, 3L * H, 0, H, cos_table, sin_table, kc, vc, H, P, d->heads, d->head_dim, d->rot, stream);
+            if (rc) return rc;
+            if (last) break;                                              // nothing downstream reads the prefix rows' last hidden states
+            rc = psalm_causal_attention_f32_split(big, 3L * H, 2 * H, 0, H, a2, 2L * K2, K2, 0, inv2, cos_table, sin_table, key_mask, attn, B, L, d->heads,
+                                                  d->head_dim, d->rot, stream);
+        } else {
+            rc = psalm_causal_attention_f32_prefix_split(big, 3L * H, 2 * H, 0, H, kc, vc, H, a2, 2L * K2, K2, 0, inv2, cos_table, sin_table, key_mask, attn,
+                                                         B, L, P, d->heads, d->head_dim, d->rot, stream);
+        }
+        if (rc) return rc;
+        float* xout = x[cur];
+        if (last || H % 64 != 0 || H > 2048) {
+            rc = psalm_gemm_x3(a2, 2L * K2, inv2, ly->w2, 2L * K2, ly->w2_scale, K2, ly->b2, xin, H, xout, H, M, H, 0, 0, gemm_workspace,
+                               gemm_workspace_bytes, stream);
+            if (rc) return rc;
+            if (last) {
+                rc = psalm_layernorm(xout, PSALM_F32, H, hidden_out, PSALM_F32, H, nullptr, 0, d->final_g, d->final_b, M, H, d->ln_eps, stream);
+            } else {
+                const psalm_phi_layer* nx = &d->layers[i + 1];
+                rc = psalm_layernorm_split(xout, H, nullptr, H, nx->ln_g, nx->ln_b, M, H, d->ln_eps, h, hinv, nullptr, 0, nullptr, nullptr, stream);
+            }
+            if (rc) return rc;
+        } else {
+            const psalm_phi_layer* nx = &d->layers[i + 1];
+            rc = psalm_gemm_x3_ln_split(a2, 2L * K2, inv2, ly->w2, 2L * K2, ly->w2_scale, K2, ly->b2, xin, H, xout, H, M, H, nx->ln_g, nx->ln_b,
+                                        d->ln_eps, nullptr, H, h, hinv, gemm_workspace, gemm_workspace_bytes, stream);
+            if (rc) return rc;
+        }
+        xin = xout;
+        cur ^= 1;
+    }
+    return 0;
+}
+
+extern "C" int psalm_phi_prefix(const psalm_phi_desc* d, const float* embeds, const unsigned char* key_mask, const float* cos_table,
+                                const float* sin_table, int P, void* cache, long cache_bytes, void* workspace, long workspace_bytes,
+                                void* gemm_workspace, long gemm_workspace_bytes, void* stream) {
+    if (phi_check(d) != 0) return -1;
+    PSALM_CHECK_ARG(embeds && key_mask && cos_table && sin_table && cache && workspace && P > 0, "psalm_phi_prefix: null argument");
+    return phi_session_pass(d, false, embeds, key_mask, cos_table, sin_table, 1, P, P, (char*)cache, cache_bytes, nullptr, workspace, workspace_bytes,
+                            gemm_workspace, gemm_workspace_bytes, stream);
+}
+
+extern "C" int psalm_phi_suffix(const psalm_phi_desc* d, const float* embeds, const unsigned char* key_mask, const float* cos_table,
+                                const float* sin_table, int N, int S, int P, const void* cache, long cache_bytes, float* hidden_out,
+                                void* workspace, long workspace_bytes, void* gemm_workspace, long gemm_workspace_bytes, void* stream) {
+    if (phi_check(d) != 0) return -1;
+    PSALM_CHECK_ARG(embeds && key_mask && cos_table && sin_table && cache && hidden_out && workspace && N > 0 && S > 0 && P > 0,
+                    "psalm_phi_suffix: null argument");
+    return phi_session_pass(d, true, embeds, key_mask, cos_table, sin_table, N, S, P, (char*)cache, cache_bytes, hidden_out, workspace,
+                            workspace_bytes, gemm_workspace, gemm_workspace_bytes, stream);
+}
+
 // ================================================================================================= Swin tower
-//   psalm_swin_forward   SwinTransformer.forward (psalm/model/visual_prompt... swin_trans.py:608-633; blocks :194-253, window attention :117-149,
+//   psalm_swin_forward  SwinTransformer.forward (psalm/model/visual_prompt... swin_trans.py:608-633; blocks :194-253, window attention :117-149,
 //                        patch merging :266-296, patch embedding :427-443) for precision "f16x3": patch im2col + GEMM + LayerNorm, then per block
 //                        { norm1 + shift + window partition -> split operand; qkv GEMM; window attention -> split operand; proj GEMM; window reverse +
 //                        residual + norm2 -> split operand; fc1 GEMM with gelu -> split operand; fc2 GEMM + residual }, per stage the output norm and

@@ -48,7 +48,7 @@ def _dt(t: torch.Tensor) -> int:
         raise PsalmHipError(f"unsupported dtype {t.dtype} (float32 / bfloat16 only)")
 
 
-ABI_VERSION = 7        # == PSALM_ABI_VERSION of include/psalm_hip.h (tests/test_0_abi.py compares the two and the built library's answer)
+ABI_VERSION = 8        # == PSALM_ABI_VERSION of include/psalm_hip.h (tests/test_0_abi.py compares the two and the built library's answer)
 
 
 class _ProfiledLib:
@@ -650,17 +650,18 @@ class Ops:
         d._keep = (layers, w)
         return d
 
-    def predictor_kv(self, desc, ms, shapes, prpos, mf, mf_size, n_reg=0, slot=0):
+    def predictor_kv(self, desc, ms, shapes, prpos, mf, mf_size, n_reg=0, slot=0, own=False):
         """The LLM-independent front of the masked-attention decoder (psalm_predictor_kv: level K / V projections + mask-feature split) into a workspace
         that `predictor_forward(..., kv=<the returned handle>)` then continues in.  `slot`: which of the caller's images this is (each keeps its own
-        workspace until its predictor call)."""
+        workspace until its predictor call).  own = True: a fresh buffer the returned handle owns instead of the binding's per-slot one (image sessions keep
+        the front across calls: the forward call only reads it)."""
         H2, W2 = mf_size
         hw = (c_int * (2 * len(shapes)))(*[int(v) for s_ in shapes for v in s_])
         self.lib.psalm_predictor_forward_workspace.restype = c_long
         nbytes = self.lib.psalm_predictor_forward_workspace(ctypes.byref(desc), hw, H2, W2, int(n_reg))
         if nbytes < 0:
             raise PsalmHipError(f"psalm_predictor_forward_workspace: {self.lib.psalm_last_error().decode()}")
-        ws = self._stage_ws(f"predictor{slot}", nbytes + 256)
+        ws = torch.empty(nbytes + 256, dtype=torch.uint8, device=self.device) if own else self._stage_ws(f"predictor{slot}", nbytes + 256)
         off = (-ws.data_ptr()) % 256
         VP = c_void_p * len(shapes)
         rc = self.lib.psalm_predictor_kv(ctypes.byref(desc), VP(*[t.data_ptr() for t in ms]), hw, VP(*[t.data_ptr() for t in prpos]), self._p(mf), H2, W2, int(n_reg),
@@ -774,6 +775,68 @@ class Ops:
                                         c_void_p(ws.data_ptr() + off), c_long(nbytes), self._p(self._gemm_ws()), c_long(self.GEMM_WS_BYTES),
                                         self._stream())
         self._check(rc, "psalm_phi_forward")
+        return out
+
+    # ---- image sessions: the Phi pass cut behind the prompt-independent prefix (psalm_phi_prefix / psalm_phi_suffix)
+    def phi_prefix_cache(self, hidden, heads, P, num_layers):
+        """A fresh prefix cache + its per-layer (K (heads, ceil32 P, 64), V (P, hidden)) float32 views; the layout is the library's
+        (psalm_phi_prefix_cache_layer_bytes: what psalm_phi_prefix writes and psalm_phi_suffix reads)."""
+        self.lib.psalm_phi_prefix_cache_layer_bytes.restype = c_long
+        kb, vb = c_long(0), c_long(0)
+        stride = self.lib.psalm_phi_prefix_cache_layer_bytes(hidden, heads, P, ctypes.byref(kb), ctypes.byref(vb))
+        if stride <= 0:
+            raise PsalmHipError("phi_prefix_cache: hidden, heads, P >= 1")
+        kb, Pp = kb.value, (P + 31) // 32 * 32
+        raw = torch.empty(stride * num_layers + 256, dtype=torch.uint8, device=self.device)
+        off = (-raw.data_ptr()) % 256
+        buf = raw[off:off + stride * num_layers]
+        views = []
+        for i in range(num_layers):
+            o0 = stride * i
+            views.append((buf[o0:o0 + heads * Pp * 64 * 4].view(torch.float32).view(heads, Pp, 64),
+                          buf[o0 + kb:o0 + kb + P * hidden * 4].view(torch.float32).view(P, hidden)))
+        return buf, views
+
+    def phi_prefix(self, desc, embeds, key_mask, cos, sin, P, cache):
+        """psalm_phi_prefix: the Phi layers over the P prefix rows as ONE native call; fills `cache` (phi_prefix_cache's buffer)."""
+        if embeds.dtype != torch.float32 or embeds.dim() != 2 or embeds.shape[0] != P or embeds.shape[1] != desc.hidden or key_mask.numel() != P:
+            raise PsalmHipError("phi_prefix: float32 (P, hidden) embeddings, key mask of P bytes")
+        self.lib.psalm_phi_prefix_workspace.restype = c_long
+        self.lib.psalm_phi_prefix_cache_bytes.restype = c_long
+        nbytes = self.lib.psalm_phi_prefix_workspace(ctypes.byref(desc), P)
+        cbytes = self.lib.psalm_phi_prefix_cache_bytes(ctypes.byref(desc), P)
+        if nbytes < 0 or cbytes < 0:
+            raise PsalmHipError(f"psalm_phi_prefix_workspace: {self.lib.psalm_last_error().decode()}")
+        if cache.numel() < cbytes or cache.data_ptr() % 256:
+            raise PsalmHipError("phi_prefix: cache of psalm_phi_prefix_cache_bytes() bytes, 256-byte aligned")
+        ws = self._stage_ws("phi_prefix", nbytes + 256)
+        off = (-ws.data_ptr()) % 256
+        rc = self.lib.psalm_phi_prefix(ctypes.byref(desc), self._p(embeds), self._p(key_mask), self._p(cos), self._p(sin), P, self._p(cache),
+                                       c_long(cache.numel()), c_void_p(ws.data_ptr() + off), c_long(nbytes), self._p(self._gemm_ws()),
+                                       c_long(self.GEMM_WS_BYTES), self._stream())
+        self._check(rc, "psalm_phi_prefix")
+
+    def phi_suffix(self, desc, embeds, key_mask, cos, sin, N, S, P, cache):
+        """psalm_phi_suffix: the Phi layers over the N*S suffix rows against the prefix cache as ONE native call: final-LayerNorm hidden states
+        (N*S, hidden) float32.  Same launches, same order, same bits as PSALM._llm_session's op-by-op sequence."""
+        if embeds.dtype != torch.float32 or embeds.dim() != 2 or embeds.shape[0] != N * S or embeds.shape[1] != desc.hidden or key_mask.numel() != N * S \
+                or cos.shape[0] < P + S:
+            raise PsalmHipError("phi_suffix: float32 (N*S, hidden) embeddings, key mask (N, S), tables of >= P + S rows")
+        self.lib.psalm_phi_suffix_workspace.restype = c_long
+        self.lib.psalm_phi_prefix_cache_bytes.restype = c_long
+        nbytes = self.lib.psalm_phi_suffix_workspace(ctypes.byref(desc), N, S)
+        cbytes = self.lib.psalm_phi_prefix_cache_bytes(ctypes.byref(desc), P)
+        if nbytes < 0 or cbytes < 0:
+            raise PsalmHipError(f"psalm_phi_suffix_workspace: {self.lib.psalm_last_error().decode()}")
+        if cache.numel() < cbytes or cache.data_ptr() % 256:
+            raise PsalmHipError("phi_suffix: cache of psalm_phi_prefix_cache_bytes() bytes, 256-byte aligned")
+        ws = self._stage_ws("phi_suffix", nbytes + 256)
+        off = (-ws.data_ptr()) % 256
+        out = self.empty(N * S, desc.hidden, dtype=torch.float32)
+        rc = self.lib.psalm_phi_suffix(ctypes.byref(desc), self._p(embeds), self._p(key_mask), self._p(cos), self._p(sin), N, S, P, self._p(cache),
+                                       c_long(cache.numel()), self._p(out), c_void_p(ws.data_ptr() + off), c_long(nbytes),
+                                       self._p(self._gemm_ws()), c_long(self.GEMM_WS_BYTES), self._stream())
+        self._check(rc, "psalm_phi_suffix")
         return out
 
     def x3_products(self, n: int):
@@ -1048,6 +1111,63 @@ class Ops:
                                                        self._p(split_inv), self._p(cos), self._p(sin), self._p(key_mask), self._p(ws),
                                                        B, L, heads, head_dim, rot, self._stream())
         self._check(rc, "psalm_causal_attention_f32_split")
+        return split_out
+
+    # ---- prefix form (image sessions): suffix rows of N prompts against one cached prefix, see psalm_causal_attention_f32_prefix
+    def _prefix_attn_ws(self, N, S, heads):
+        self.lib.psalm_causal_attention_f32_prefix_workspace.restype = c_long
+        nbytes = self.lib.psalm_causal_attention_f32_prefix_workspace(N, S, heads)
+        key = ("causal_prefix_ws", nbytes)         # (as causal_f32_ws: one per binding -- a binding serves one stream at a time, PSALM.replica)
+        ws = self._ws.get(key)
+        if ws is None:
+            ws = self._ws[key] = torch.empty(nbytes, dtype=torch.uint8, device=self.device)
+        return ws
+
+    @staticmethod
+    def _check_prefix_cache(k_cache, v_cache, P, heads):
+        Pp = (P + 31) // 32 * 32
+        if (k_cache.dtype != torch.float32 or v_cache.dtype != torch.float32 or not k_cache.is_contiguous() or k_cache.numel() != heads * Pp * 64
+                or v_cache.dim() != 2 or v_cache.shape[0] != P or v_cache.shape[1] < heads * 64 or v_cache.stride(1) != 1):
+            raise PsalmHipError("prefix cache: K (heads, ceil32(P), 64) float32 contiguous, V (P, >= heads*64) float32 rows")
+
+    def phi_prefix_kv_store(self, buf, k_off, v_off, cos, sin, k_cache, v_cache, P, heads, head_dim, rot):
+        """One layer's prefix cache from the [k|v|q|..] buffer of the P prefix rows: k_cache <- RoPE(k) as (heads, ceil32(P), 64), v_cache <- v rows."""
+        if buf.dtype != torch.float32 or buf.shape[0] < P:
+            raise PsalmHipError("phi_prefix_kv_store: float32 buffer of >= P rows")
+        self._check_prefix_cache(k_cache, v_cache, P, heads)
+        rc = self.lib.psalm_phi_prefix_kv_store(self._pv(buf), c_long(buf.stride(0)), k_off, v_off, self._p(cos), self._p(sin), self._p(k_cache),
+                                                self._pv(v_cache), c_long(v_cache.stride(0)), P, heads, head_dim, rot, self._stream())
+        self._check(rc, "psalm_phi_prefix_kv_store")
+
+    def causal_attention_prefix(self, buf, q_off, k_off, v_off, k_cache, v_cache, out, o_off, cos, sin, key_mask, N, S, P, heads, head_dim, rot):
+        """buf (N*S, ld) float32 holds the suffix rows' q|k|v column blocks; k_cache / v_cache: the shared prefix of P rows; cos / sin (>= P+S, rot);
+        key_mask (N, S) u8.  out (N*S, ldo) float32 receives the attention output at column o_off (may be `buf`: q is read before it is written)."""
+        if buf.dtype != torch.float32 or out.dtype != torch.float32 or cos.shape[0] < P + S or key_mask.numel() != N * S:
+            raise PsalmHipError("causal_attention_prefix: float32 buffers, cos / sin tables of >= P + S rows, key_mask (N, S)")
+        self._check_prefix_cache(k_cache, v_cache, P, heads)
+        ws = self._prefix_attn_ws(N, S, heads)
+        rc = self.lib.psalm_causal_attention_f32_prefix(self._pv(buf), c_long(buf.stride(0)), q_off, k_off, v_off, self._p(k_cache),
+                                                        self._pv(v_cache), c_long(v_cache.stride(0)), self._pv(out), c_long(out.stride(0)), o_off,
+                                                        self._p(cos), self._p(sin), self._p(key_mask), self._p(ws), N, S, P, heads, head_dim, rot,
+                                                        self._stream())
+        self._check(rc, "psalm_causal_attention_f32_prefix")
+        return out
+
+    def causal_attention_prefix_split(self, buf, q_off, k_off, v_off, k_cache, v_cache, split_out, split_inv, split_col_off, cos, sin, key_mask,
+                                      N, S, P, heads, head_dim, rot):
+        """causal_attention_prefix whose output goes, in split-f16 form under the row scales 1/split_inv, into columns split_col_off.. of
+        `split_out` ((N*S, 2*Kp) float16; lo part Kp columns further)."""
+        if (buf.dtype != torch.float32 or split_out.dtype != torch.float16 or split_inv.dtype != torch.float32 or cos.shape[0] < P + S
+                or key_mask.numel() != N * S):
+            raise PsalmHipError("causal_attention_prefix_split: float32 qkv buffer, float16 split buffer, float32 scales, tables of >= P + S rows")
+        self._check_prefix_cache(k_cache, v_cache, P, heads)
+        ws = self._prefix_attn_ws(N, S, heads)
+        rc = self.lib.psalm_causal_attention_f32_prefix_split(self._pv(buf), c_long(buf.stride(0)), q_off, k_off, v_off, self._p(k_cache),
+                                                              self._pv(v_cache), c_long(v_cache.stride(0)), self._p(split_out),
+                                                              c_long(split_out.stride(0)), split_out.shape[1] // 2, split_col_off,
+                                                              self._p(split_inv), self._p(cos), self._p(sin), self._p(key_mask), self._p(ws),
+                                                              N, S, P, heads, head_dim, rot, self._stream())
+        self._check(rc, "psalm_causal_attention_f32_prefix_split")
         return split_out
 
     def mha_attention(self, q, k, v, B, Lq, Lk, heads, mask=None, row_all_masked=None):

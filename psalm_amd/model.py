@@ -109,6 +109,31 @@ class _VisionTower:
         return self
 
 
+class ImageSession:
+    """What `PSALM.encode_image` keeps on the device for one image, so that `PSALM.segment` runs only the prompt-dependent part of the model:
+    the four Swin levels (`feats`), the projector's image tokens, the pixel decoder's outputs (`mask_features`, `multi_scale_features` + sizes),
+    the predictor's K / V front per region count (built lazily) and the Phi prefix cache -- RoPE'd K and V of the prompt-independent first P rows
+    (system text + image tokens) of every layer, built on the first `segment` call and reused while the leading text ids stay the same
+    (`prefix_builds` / `prefix_hits` count both).  Belongs to the model (or replica) that made it."""
+
+    def __init__(self, model, images, seg_info, feats, image_tokens, n_img, pd):
+        self.model, self.version = model, model._weights_version
+        self.images, self.seg_info = images, seg_info
+        self.feats, self.image_tokens, self.n_img = feats, image_tokens, n_img
+        self.mask_features, self.multi_scale_features, self.shapes, self.mask_features_size = pd
+        self.kv = {}                              # region count -> predictor K / V handle (session-owned workspace)
+        self.prefix_key = None                    # tuple of the leading text ids the cache below was built for
+        self.prefix_len = 0                       # P
+        self.prefix_cache = None                  # (buffer, per-layer (K (heads, ceil32 P, 64), V (P, hidden)) views)
+        self.prefix_builds = self.prefix_hits = 0
+
+    def nbytes(self) -> int:
+        """device bytes held: vision tensors + K / V fronts + prefix cache (2 * layers * P * hidden * 4 up to padding)"""
+        ts = [t for t, _, _ in self.feats] + [self.image_tokens, self.mask_features] + list(self.multi_scale_features)
+        n = sum(t.numel() * t.element_size() for t in ts) + sum(h[0][0].numel() for h in self.kv.values() if h is not None)
+        return n + (self.prefix_cache[0].numel() if self.prefix_cache is not None else 0)
+
+
 class PSALM:
     # The default is the mode that meets the reference's fp32 results to the north star's tolerance; "bf16" is the faster, looser mode.
     DEFAULT_PRECISION = "f16x3"
@@ -185,6 +210,10 @@ class PSALM:
         self.image_processor = None                   # dict of pre-processors, set by from_pretrained / load_pretrained_model
         self.training = False
         self._prepare_weights(state_dict)
+
+    @property
+    def _weights_version(self) -> int:
+        return self._weights_epoch[0]
 
     def replica(self) -> "PSALM":
         """A second instance of this model for ANOTHER HIP stream / host thread (two images in flight on one GPU: the hardware interleaves the
@@ -325,6 +354,11 @@ class PSALM:
             del self._cache[k]
         if getattr(self, "_graphs", None):
             self._graphs.clear()
+        # live ImageSessions hold tensors derived from the old weights: invalid.  (A one-element list: replicas share it as they share `w`, so
+        #  preparing the weights again through any of them invalidates the sessions of all.)
+        if not hasattr(self, "_weights_epoch"):
+            self._weights_epoch = [0]
+        self._weights_epoch[0] += 1
 
         def lin(dst, src, bias=True, small=False, pair=False):
             wt, bs = sd[src + ".weight"], (sd[src + ".bias"] if bias and (src + ".bias") in sd else None)
@@ -1198,27 +1232,8 @@ class PSALM:
                 arrays[name + "_off"], arrays[name + "_rows"] = plan[name]
         post = []
         if seg_info is not None:
-            div = cfg.size_divisibility
-            Hpad, Wpad = (Hi + div - 1) // div * div, (Wi + div - 1) // div * div     # ImageList.from_tensors(images, 32), LP:1400
-            for info in seg_info:
-                pm = info.get("padding_mask")
-                if pm is None:
-                    oh, ow = Hi, Wi
-                else:                                     # extent of the un-padded box (LP:1418-1423), via row / column projections
-                    valid = ~np.asarray(pm.cpu() if torch.is_tensor(pm) else pm, dtype=bool)
-                    rows, cols = np.flatnonzero(valid.any(1)), np.flatnonzero(valid.any(0))
-                    oh, ow = int(rows[-1] - rows[0] + 1), int(cols[-1] - cols[0] + 1)
-                post.append((Hpad, Wpad, oh, ow, int(info.get("height", Hi)), int(info.get("width", Wi))))
-        layout, off = {}, 0
-        for k, a in arrays.items():
-            a = np.ascontiguousarray(a)
-            arrays[k] = a
-            layout[k] = (off, a.size, a.dtype.str)
-            off = (off + a.nbytes + 15) // 16 * 16
-        blob = np.zeros(max(off, 16), np.uint8)
-        for k, a in arrays.items():
-            o0 = layout[k][0]
-            blob[o0:o0 + a.nbytes] = a.view(np.uint8).reshape(-1)
+            post = [self._post_sizes(Hi, Wi, info, cfg.size_divisibility) for info in seg_info]
+        blob, layout = self._pack(arrays)
         meta = {"B": B, "L": plan["L"], "lens": plan["lens"], "n_img": n_img, "n_cls": tuple(plan["n_cls"]),
                 "n_regions": tuple(n_regions) if n_regions is not None else None, "post": tuple(post),
                 "img_shape": tuple(images.shape), "layout": tuple(sorted(layout.items())), "video": video}
@@ -1356,6 +1371,323 @@ class PSALM:
                                            video=vp_images is not None)
         dv = self._views(torch.from_numpy(blob).to(self.device), layout)
         return self._forward_device(images, dv, meta, stages=stages, postprocess=False, vp_images=vp_images)
+
+    # ======================================================================================= image sessions: encode once, segment many prompts
+    def _session_mode_check(self):
+        if self.precision == "bf16":
+            raise NotImplementedError("image sessions: precision 'bf16' is a side line with its own attention kernels (f16x3 / fp32 only)")
+        if self.llm_products != 3:
+            raise NotImplementedError("image sessions: llm_products=1 is a side mode of the one-shot path (llm_products=3 only)")
+
+    @torch.no_grad()
+    def encode_image(self, images, seg_info=None) -> "ImageSession":
+        """Everything of eval_seg that does not read the prompt, for ONE image ((1, 3, H, W) or (3, H, W), pre-processed as for eval_seg; `seg_info`: its
+        geometry entry -- a dict, or a list holding it): Swin, projector, pixel decoder.  Returns the ImageSession `segment` takes."""
+        self._session_mode_check()
+        if images.dim() == 3:
+            images = images[None]
+        if images.dim() != 4 or images.shape[0] != 1:
+            raise ValueError("encode_image: one image, (1, 3, H, W) or (3, H, W)")
+        if isinstance(seg_info, (list, tuple)):
+            if len(seg_info) != 1:
+                raise ValueError("encode_image: seg_info of one image")
+            seg_info = seg_info[0]
+        images = images.to(self.device, torch.float32).contiguous()
+        feats = self.swin(images)
+        res5, h5, w5 = feats[3]
+        img_tok, n_img = self.projector(res5, 1, h5, w5)
+        pd = self.pixel_decoder([(tok, h, w_) for tok, h, w_ in feats])
+        return ImageSession(self, images, seg_info, feats, img_tok, n_img, pd)
+
+    def _session_kv(self, session, n_reg):
+        """the predictor's K / V front for this region count, in a workspace the session owns (built on first use)"""
+        if n_reg not in session.kv:
+            mf, ms, shapes, mfs = session.mask_features, session.multi_scale_features, session.shapes, session.mask_features_size
+            kv = None
+            if self.kv_side and self._predictor_native_ok(mf):
+                desc, prpos = self._predictor_desc(shapes)
+                cont = lambda t: t if t.is_contiguous() else t.contiguous()       # noqa: E731
+                ms_c, mf_c = [cont(t) for t in ms], cont(mf)
+                kv = (self.ops.predictor_kv(desc, ms_c, shapes, prpos, mf_c, mfs, n_reg, slot=0, own=True), ms_c, mf_c)
+            session.kv[n_reg] = kv
+        return session.kv[n_reg]
+
+    @staticmethod
+    def _pack(arrays):
+        """the host arrays of one call as ONE byte blob (one host-to-device copy) + its layout: name -> (offset, elements, dtype)"""
+        layout, off = {}, 0
+        for k, a in arrays.items():
+            a = np.ascontiguousarray(a)
+            arrays[k] = a
+            layout[k] = (off, a.size, a.dtype.str)
+            off = (off + a.nbytes + 15) // 16 * 16
+        blob = np.zeros(max(off, 16), np.uint8)
+        for k, a in arrays.items():
+            o0 = layout[k][0]
+            blob[o0:o0 + a.nbytes] = a.view(np.uint8).reshape(-1)
+        return blob, layout
+
+    def _session_plan(self, session, input_ids, attention_mask, class_name_ids, cls_indices, token_refer_id, n_regions, want_cls, want_refer):
+        """The splice plan of N prompts on the session's image, cut at P = the row just past the last image row: the shared prefix's (sid, srow) and
+        its key (the leading text ids), and the suffix plan -- (N, S) arrays with S bucketed by `len_bucket` as `_bucketed` does for L, row sets
+        re-based from absolute to suffix positions."""
+        ids = input_ids.cpu().numpy().astype(np.int64)
+        N, T = ids.shape
+        n_img = session.n_img
+        t_img = []
+        for b in range(N):
+            pos = np.flatnonzero(ids[b] == IMAGE_TOKEN_INDEX)
+            if pos.shape[0] != 1:
+                raise ValueError(f"segment: prompt {b} holds {pos.shape[0]} <image> tokens, a session prompt has exactly one")
+            if (ids[b, :pos[0]] < 0).any():
+                raise ValueError(f"segment: prompt {b} has a special token at position {int(np.flatnonzero(ids[b, :pos[0]] < 0)[0])}, before <image>: "
+                                 "the shared prefix is text + <image>")
+            t_img.append(int(pos[0]))
+        for b in range(1, N):
+            n = min(t_img[0], t_img[b]) + 1
+            diff = np.flatnonzero(ids[b, :n] != ids[0, :n])
+            if diff.shape[0] or t_img[b] != t_img[0]:
+                at = int(diff[0]) if diff.shape[0] else n
+                raise ValueError(f"segment: prompt {b} differs from prompt 0 at token position {at}; all prompts of a call must share the rows up to "
+                                 "and including <image>")
+        key = tuple(int(v) for v in ids[0, :t_img[0]])
+        P = t_img[0] + n_img
+        plan = self._splice_plan(input_ids, attention_mask, n_img, class_name_ids, cls_indices, token_refer_id, n_regions, want_cls, want_refer)
+        L = plan["L"]
+        if not plan["kmask"][:, :P].all():
+            raise ValueError("segment: the attention mask hides a row of the shared prefix (prefix rows are always real)")
+        S = L - P
+        if S < 1:
+            raise ValueError("segment: nothing follows <image>")
+        q = max(int(self.len_bucket or 0), 1)
+        Sb = (S + q - 1) // q * q
+        sid = np.full((N, Sb), -1, np.int32)
+        srow = np.zeros((N, Sb), np.int32)
+        kmask = np.zeros((N, Sb), np.uint8)
+        sid[:, :S], srow[:, :S], kmask[:, :S] = plan["sid"][:, P:], plan["srow"][:, P:], plan["kmask"][:, P:]
+        psrow = plan["srow"][0, :P].copy()
+        psrow[plan["sid"][0, :P] == 1] %= n_img                   # (one image: its tokens are rows 0 .. n_img-1 whatever the prompt index)
+        out = {"P": P, "S": Sb, "S_real": S, "lens": [l_ - P for l_ in plan["lens"]], "key": key, "n_cls": plan["n_cls"],
+               "prefix": (plan["sid"][0, :P].copy(), psrow), "sid": sid, "srow": srow, "kmask": kmask}
+        for name in ("seg", "cls", "refer", "region"):
+            if plan[name] is None:
+                out[name] = None
+                continue
+            off, rows = plan[name]
+            r64 = rows.astype(np.int64)
+            assert (r64 % L >= P).all(), "row sets live behind the prefix"
+            rows = (r64 // L * Sb + r64 % L - P).astype(np.int32)
+            if name != "seg" and q > 1:
+                n = (rows.shape[0] + q - 1) // q * q
+                rows = np.concatenate((rows, np.zeros(max(n, q) - rows.shape[0], np.int32)))
+            out[name] = (off, rows)
+        return out
+
+    def _phi_session_desc(self):
+        o, w, cfg = self.ops, self.w, self.cfg
+        key = ("phi_desc",)
+        if key not in self._cache:                # (the descriptor PSALM.llm builds: shared)
+            self._cache[key] = o.phi_desc([dict(w1=w[f"llm{i}.w1"], b1=w[f"llm{i}.b1"], w2=w[f"llm{i}.w2"], b2=w[f"llm{i}.b2"],
+                                                ln_g=w[f"llm{i}.ln.g"], ln_b=w[f"llm{i}.ln.b"], bnd=w[f"llm{i}.bnd"],
+                                                paired=self.paired.get(f"llm{i}", False)) for i in range(cfg.num_layers)],
+                                          cfg.hidden_size, cfg.intermediate_size, cfg.num_heads, cfg.head_dim, cfg.rotary_dim, cfg.layer_norm_eps,
+                                          w["llm.final.g"], w["llm.final.b"])
+        return self._cache[key]
+
+    def _llm_session(self, embeds, key_mask, B, L, P, cache, suffix: bool):
+        """PSALM.llm cut behind the prompt-independent prefix.  suffix = False: the P prefix rows (B = 1, L = P), every layer's RoPE'd K and its V go
+        into `cache` (Ops.phi_prefix_cache), the last layer stops behind its [k|v|q|fc1] GEMM; returns None.  suffix = True: the B * L suffix rows
+        at positions P .., attention through the prefix kernel against `cache`; returns the final-LayerNorm hidden states (B*L, hidden).
+        One native call each (psalm_phi_prefix / psalm_phi_suffix) under the conditions of PSALM.llm's stage-level call, else this op-by-op
+        sequence -- same launches, same bits (tests/test_11_session_emu.py)."""
+        o, w, cfg = self.ops, self.w, self.cfg
+        Hd, I = cfg.hidden_size, cfg.intermediate_size
+        if cfg.head_dim != 64 or cfg.rotary_dim != 32:
+            raise NotImplementedError("image sessions: the prefix attention kernel is built for head_dim 64 / rotary dim 32 (Phi-1.5)")
+        cos, sin = self._rope(P + L if suffix else P)
+        buf, views = cache
+        nh, hd, rd = cfg.num_heads, cfg.head_dim, cfg.rotary_dim
+        fuse_split = self.fuse_split and (Hd + I) % 64 == 0 and Hd % 8 == 0 and "llm0.bnd" in w
+        if fuse_split and self.c_stages and self.x3 and getattr(o.lib, "records", None) is None and not (H._DEBUG_BOUNDS or o.debug_bounds) \
+                and key_mask.is_contiguous():
+            desc = self._phi_session_desc()
+            if suffix:
+                return o.phi_suffix(desc, embeds, key_mask, cos, sin, B, L, P, buf)
+            o.phi_prefix(desc, embeds, key_mask, cos, sin, P, buf)
+            return None
+        x = embeds
+        big = o.empty(B * L, 3 * Hd if fuse_split else 3 * Hd + I, dtype=torch.float32)
+        if fuse_split:
+            a2 = o.empty(B * L, 2 * (Hd + I), dtype=torch.float16)
+            inv2 = o.empty(B * L, dtype=torch.float32)
+        if self.paired.get("llm0", False) and not fuse_split:
+            raise H.PsalmHipError("the Phi fc1 rows are laid out for paired split-f16 stores but the fused operand hand-over is off "
+                                  "(build the model with paired_split_stores=False)")
+        if self.x3:
+            h = o.layernorm_split(x, w["llm0.ln.g"], w["llm0.ln.b"], cfg.layer_norm_eps)[1]
+        else:
+            h = o.layernorm(x, w["llm0.ln.g"], w["llm0.ln.b"], cfg.layer_norm_eps, out_dtype=self.adt)
+        for i in range(cfg.num_layers):
+            last = i == cfg.num_layers - 1
+            ng, nb = (w["llm.final.g"], w["llm.final.b"]) if last else (w[f"llm{i + 1}.ln.g"], w[f"llm{i + 1}.ln.b"])
+            kc, vc = views[i]
+            if fuse_split:
+                o.gemm_x3_split(h, w[f"llm{i}.w1"], w[f"llm{i}.b1"], H.ACT_GELU_NEW, a2, inv2, w[f"llm{i}.bnd"], split_col_off=Hd,
+                                split_col_start=3 * Hd, act_col_start=3 * Hd, out=big, global_rows=True, paired=self.paired.get(f"llm{i}", False))
+                if suffix:
+                    o.causal_attention_prefix_split(big, 2 * Hd, 0, Hd, kc, vc, a2, inv2, 0, cos, sin, key_mask, B, L, P, nh, hd, rd)
+                else:
+                    o.phi_prefix_kv_store(big, 0, Hd, cos, sin, kc, vc, P, nh, hd, rd)
+                    if last:
+                        break
+                    o.causal_attention_split(big, 2 * Hd, 0, Hd, a2, inv2, 0, cos, sin, key_mask, B, L, nh, hd, rd)
+                if last or Hd % 64 != 0 or Hd > 2048:
+                    x = o.gemm(H.SplitF16(a2, inv2, Hd + I), w[f"llm{i}.w2"], w[f"llm{i}.b2"], residual=x, out_dtype=torch.float32)
+                    h = o.layernorm(x, ng, nb, cfg.layer_norm_eps, out_dtype=torch.float32) if last else \
+                        o.layernorm_split(x, ng, nb, cfg.layer_norm_eps)[1]
+                else:
+                    x, h, _ = o.gemm_x3_ln_split(H.SplitF16(a2, inv2, Hd + I), w[f"llm{i}.w2"], w[f"llm{i}.b2"], x, ng, nb, cfg.layer_norm_eps)
+                continue
+            o.gemm(h, w[f"llm{i}.w1"], w[f"llm{i}.b1"], act=H.ACT_GELU_NEW, act_col_start=3 * Hd, out=big)
+            # columns: [k | v | q | gelu_new(fc1)];  attention output overwrites q in place (q was copied out by the RoPE pre-pass)
+            if suffix:
+                o.causal_attention_prefix(big, 2 * Hd, 0, Hd, kc, vc, big, 2 * Hd, cos, sin, key_mask, B, L, P, nh, hd, rd)
+            else:
+                o.phi_prefix_kv_store(big, 0, Hd, cos, sin, kc, vc, P, nh, hd, rd)
+                if last:
+                    break
+                o.causal_attention(big, 2 * Hd, 0, Hd, big, 2 * Hd, cos, sin, key_mask, B, L, nh, hd, rd)
+            x = o.gemm(big[:, 2 * Hd:], w[f"llm{i}.w2"], w[f"llm{i}.b2"], residual=x, out_dtype=torch.float32)
+            if self.x3 and not last:
+                h = o.layernorm_split(x, ng, nb, cfg.layer_norm_eps)[1]
+            else:
+                h = o.layernorm(x, ng, nb, cfg.layer_norm_eps, out_dtype=torch.float32)
+        return h if suffix else None
+
+    def _session_prefix(self, session, sp):
+        """the session's Phi prefix cache for this call's leading text ids: reused when the key matches, (re)built otherwise"""
+        o, w, cfg = self.ops, self.w, self.cfg
+        if session.prefix_cache is not None and session.prefix_key == sp["key"] and session.prefix_len == sp["P"]:
+            session.prefix_hits += 1
+            return session.prefix_cache
+        P = sp["P"]
+        psid, psrow = sp["prefix"]
+        cache = session.prefix_cache
+        session.prefix_key = None                 # (the buffer is rebuilt in place: not a hit for the old text if the pass below raises midway)
+        if cache is None or session.prefix_len != P:
+            cache = o.phi_prefix_cache(cfg.hidden_size, cfg.num_heads, P, cfg.num_layers)
+        embeds = o.gather_rows([w["embed"], session.image_tokens, w["seg_query"], None], self._dev_i32(psid), self._dev_i32(psrow), cfg.hidden_size,
+                               out_dtype=torch.float32)
+        ones = torch.ones(1, P, dtype=torch.uint8, device=self.device)
+        self._llm_session(embeds, ones, 1, P, P, cache, suffix=False)
+        session.prefix_cache, session.prefix_key, session.prefix_len = cache, sp["key"], P
+        session.prefix_builds += 1
+        return cache
+
+    @staticmethod
+    def _post_sizes(Hi, Wi, info, div):
+        """the post-processing geometry of one image: padded size, extent of the un-padded box, original size"""
+        Hpad, Wpad = (Hi + div - 1) // div * div, (Wi + div - 1) // div * div         # ImageList.from_tensors(images, 32), LP:1400
+        pm = info.get("padding_mask")
+        if pm is None:
+            oh, ow = Hi, Wi
+        else:                                             # extent of the un-padded box (LP:1418-1423), via row / column projections
+            valid = ~np.asarray(pm.cpu() if torch.is_tensor(pm) else pm, dtype=bool)
+            rows, cols = np.flatnonzero(valid.any(1)), np.flatnonzero(valid.any(0))
+            oh, ow = int(rows[-1] - rows[0] + 1), int(cols[-1] - cols[0] + 1)
+        return (Hpad, Wpad, oh, ow, int(info.get("height", Hi)), int(info.get("width", Wi)))
+
+    @torch.no_grad()
+    def segment(self, session: "ImageSession", input_ids, attention_mask=None, *, seg_info=None, class_name_ids=None,
+                class_name_embedding_indices=None, cls_indices=None, token_refer_id=None, refer_embedding_indices=None, is_thing_list=None,
+                labels=None, region_point_sampler: Callable = default_region_point_sampler, postprocess: bool = True,
+                stages: Optional[dict] = None):
+        """N >= 1 prompts of the model's task on the session's image: what `eval_seg` returns for a batch of N copies of that image with these
+        prompts (a list of N result dicts), without running the vision side again and with a Phi pass over the rows behind the shared prefix
+        only.  Prompt-side keywords as eval_seg; `seg_info`: per prompt (region masks / ground truth under "instances", geometry), default the
+        session's entry for every prompt.  All prompts must agree on the tokens up to and including their one <image> (ValueError otherwise).
+        postprocess=False: the predictor outputs per prompt, as `forward_logits`; `stages`: filled as by `forward_logits(stages=...)` with the
+        suffix rows' `inputs_embeds` / `hidden_states`."""
+        self._session_mode_check()
+        if not isinstance(session, ImageSession) or session.model is not self:
+            raise ValueError("segment: this session was made by another model (or replica)")
+        if session.version != self._weights_version:
+            raise ValueError("segment: the model's weights were prepared again after this session was made; encode the image again")
+        if self.seg_task == "panoptic" and postprocess:
+            assert is_thing_list is not None, "is_thing_list need to be given"
+            self.is_thing_list = is_thing_list
+        o, w, cfg = self.ops, self.w, self.cfg
+        if input_ids.dim() == 1:
+            input_ids = input_ids[None]
+        N = int(input_ids.shape[0])
+        if seg_info is None:
+            seg_info = [session.seg_info if session.seg_info is not None else {}] * N
+        if len(seg_info) != N:
+            raise ValueError("segment: one seg_info entry per prompt")
+        n_img = session.n_img
+        arrays = {}
+        n_regions = None
+        if bool((input_ids == REGION_TOKEN_INDEX).any()):
+            pts, n_regions = self.region_points([s_["instances"].region_masks.tensor for s_ in seg_info], region_point_sampler)
+            arrays["region_img"] = np.zeros(sum(n_regions), np.int32)                 # every region pools from the session's image
+            arrays["region_pts"] = np.ascontiguousarray(pts.numpy(), np.float32)
+        sp = self._session_plan(session, input_ids, attention_mask, class_name_ids, cls_indices, token_refer_id, n_regions,
+                                class_name_embedding_indices is not None, refer_embedding_indices is not None)
+        P, S = sp["P"], sp["S"]
+        arrays["sid"], arrays["srow"], arrays["kmask"] = sp["sid"].reshape(-1), sp["srow"].reshape(-1), sp["kmask"].reshape(-1)
+        for name in ("seg", "cls", "refer", "region"):
+            if sp[name] is not None:
+                arrays[name + "_off"], arrays[name + "_rows"] = sp[name]
+        blob, layout = self._pack(arrays)
+        dv = self._views(torch.from_numpy(blob).to(self.device), layout)
+        cache = self._session_prefix(session, sp)
+        region_feats = None
+        if n_regions is not None:
+            side = int(math.sqrt(n_img))
+            region_feats = o.region_pool(session.image_tokens, dv["region_img"], dv["region_pts"].view(sum(n_regions), -1, 2), side, side, n_img)
+        embeds = o.gather_rows([w["embed"], session.image_tokens, w["seg_query"], region_feats], dv["sid"], dv["srow"], cfg.hidden_size,
+                               out_dtype=torch.float32)
+        hidden = self._llm_session(embeds, dv["kmask"].view(N, S), N, S, P, cache, suffix=True)
+        if stages is not None:
+            Sr = sp["S_real"]
+            stages.update(feats=session.feats, image_tokens=session.image_tokens, prefix_len=P, lengths=sp["lens"],
+                          inputs_embeds=embeds.view(N, S, -1)[:, :Sr], hidden_states=hidden.view(N, S, -1)[:, :Sr])
+        Q = cfg.md_queries
+        seg_q = o.gemm(o.segment_mean(hidden, dv["seg_off"], dv["seg_rows"], out_dtype=self.adt), w["seg_query_projector.w"],
+                       w["seg_query_projector.b"], out_dtype=torch.float32)
+        cls_emb = seg_emb = reg_emb = None
+        if "cls_off" in dv:
+            cls_emb = o.gemm(o.segment_mean(hidden, dv["cls_off"], dv["cls_rows"], out_dtype=self.adt), w["class_name_projector.w"],
+                             w["class_name_projector.b"], out_dtype=self.wdt)
+        if "refer_off" in dv:
+            seg_emb = o.gemm(o.segment_mean(hidden, dv["refer_off"], dv["refer_rows"], out_dtype=self.adt), w["SEG_token_projector.w"],
+                             w["SEG_token_projector.b"], out_dtype=self.wdt)
+        if "region_off" in dv:
+            reg_emb = o.gemm(o.segment_mean(hidden, dv["region_off"], dv["region_rows"], out_dtype=self.adt), w["region_projector.w"],
+                             w["region_projector.b"], out_dtype=self.adt)
+        if stages is not None:
+            stages.update(seg_query=seg_q.view(N, Q, -1), class_name_embedding=cls_emb, SEG_embedding=seg_emb, region_embedding=reg_emb,
+                          mask_features=[session.mask_features] * N, multi_scale_features=[session.multi_scale_features] * N)
+        mf, ms, shapes, mfs = session.mask_features, session.multi_scale_features, session.shapes, session.mask_features_size
+        Hi, Wi = int(session.images.shape[2]), int(session.images.shape[3])
+        outs = []
+        c0 = r0 = 0
+        for b in range(N):
+            nc = sp["n_cls"][b]
+            ce = cls_emb[c0:c0 + nc] if cls_emb is not None else None
+            c0 += nc
+            se = seg_emb[b:b + 1] if seg_emb is not None else None
+            re = None
+            if reg_emb is not None:
+                re = reg_emb[r0:r0 + n_regions[b]]
+                r0 += n_regions[b]
+            r = self.predictor(ms, shapes, mf, mfs, seg_q[b * Q:(b + 1) * Q], se, ce, re, kv=self._session_kv(session, n_regions[b] if n_regions else 0))
+            if not postprocess:
+                outs.append(r)
+                continue
+            res = self._postprocess(r, self._post_sizes(Hi, Wi, seg_info[b], cfg.size_divisibility))
+            outs.append(self._finalize(res, seg_info[b]))
+        return outs
 
     # ======================================================================================= post-processing + eval_seg
     def _semantic(self, mflat, probsT, Kpad, want_mask_score=False):

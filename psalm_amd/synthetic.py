@@ -361,3 +361,40 @@ def make_inputs(cfg: PsalmConfig, task: str = "panoptic", size: int = 1024, batc
     if task == "referring":
         out["refer_embedding_indices"] = (input_ids == REFER_TOKEN_INDEX).to(torch.int64)
     return out
+
+
+# ---- image sessions (PSALM.encode_image / PSALM.segment): N prompts on ONE image
+def session_inputs(cfg, task, n, size=96, seed=4, num_classes=9):
+    """make_inputs for a batch of n, turned into n prompts on ONE image: image 0 n times, every prompt's tokens up to <image> replaced by
+    prompt 0's (make_inputs draws them per prompt), right-padded again.  The result feeds eval_seg (N copies of the image) as it is;
+    PSALM.segment takes it without `images` / `labels`."""
+    from .prompts import IMAGE_TOKEN_INDEX
+    inp = make_inputs(cfg, task, size=size, batch=n, seed=seed, num_classes=num_classes)
+    ids, am = inp["input_ids"], inp["attention_mask"]
+    rows = []
+    head = None
+    for b in range(n):
+        r = ids[b][am[b]].tolist()
+        t = r.index(IMAGE_TOKEN_INDEX)
+        head = r[:t + 1] if head is None else head
+        rows.append(head + r[t + 1:])
+    T = max(len(r) for r in rows)
+    new_ids = torch.zeros(n, T, dtype=torch.int64)
+    new_am = torch.zeros(n, T, dtype=torch.bool)
+    for b, r in enumerate(rows):
+        new_ids[b, :len(r)] = torch.tensor(r)
+        new_am[b, :len(r)] = True
+    inp["input_ids"], inp["attention_mask"], inp["labels"] = new_ids, new_am, new_ids.clone()
+    inp["images"] = inp["images"][:1].repeat(n, 1, 1, 1)
+    return inp
+
+
+def fix_indices(inp):
+    """the *_embedding_indices tensors only signal presence to the model and the oracle; rebuild them from the new ids with the project's constants"""
+    from . import prompts as PR
+    ids = inp["input_ids"]
+    if "class_name_embedding_indices" in inp:
+        inp["class_name_embedding_indices"] = (ids == PR.CLS_TOKEN_INDEX).to(torch.int64)
+    if "refer_embedding_indices" in inp:
+        inp["refer_embedding_indices"] = (ids == PR.REFER_TOKEN_INDEX).to(torch.int64)
+    return inp
