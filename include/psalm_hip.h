@@ -32,8 +32,9 @@ const char* psalm_last_error(void);
  * 7: psalm_set_tuning / psalm_get_tuning, psalm_layernorm_chain, psalm_gemm_f32_pair, psalm_postprocess*, psalm_predictor_kv + the kv_ready argument of
  *    psalm_predictor_forward (r06).
  * 8: image sessions: psalm_causal_attention_f32_prefix[_split] (+ _workspace), psalm_phi_prefix_kv_store, the stage-level psalm_phi_prefix /
- *    psalm_phi_suffix (+ their _workspace / _cache_bytes functions). */
-#define PSALM_ABI_VERSION 8
+ *    psalm_phi_suffix (+ their _workspace / _cache_bytes functions).
+ * 9: video object tracking: psalm_video_pick, psalm_video_fuse (+ _workspace), psalm_mask_resize_nearest_pad, psalm_mask_select_points. */
+#define PSALM_ABI_VERSION 9
 int psalm_abi_version(void);
 const char* psalm_backend(void); /* "hip-gfx950" */
 
@@ -639,6 +640,33 @@ int psalm_postprocess_instance(const psalm_post_desc* d, const psalm_post_io* io
 int psalm_postprocess_panoptic(const psalm_post_desc* d, const psalm_post_io* io, int* mask_pred_is, void* workspace, long workspace_bytes, void* stream);
 int psalm_postprocess_referring(const psalm_post_desc* d, const psalm_post_io* io, int* mask_pred_is, void* workspace, long workspace_bytes, void* stream);
 int psalm_postprocess_region(const psalm_post_desc* d, const psalm_post_io* io, int* mask_pred_is, void* workspace, long workspace_bytes, void* stream);
+
+/* ------------------------------------------------------------------------------------------------------------------
+ * Video object tracking (csrc/video.hip; psalm_amd/video.py): the per-frame bookkeeping of the reference's DAVIS driver with memory
+ * (psalm/eval/eval_davis.py:388-480), on the device.  Integer results are exact against the host formulas. */
+/* eval_davis.py:443-457.  scores (Q,R) f32 (`instances.scores` of the region task, NaN-free), 10 <= Q <= 1024, 1 <= R <= 32.  Objects in index
+ * order; each takes, of its ten best queries in descending score order (equal scores: lowest query first), the first that no earlier object took.
+ * An object whose ten best are all taken repeats the previous object's pick and score (the reference's loop does).  pick_query (R) i32, pick_score (R) f32. */
+int psalm_video_pick(const float* scores, int Q, int R, int* pick_query, float* pick_score, void* stream);
+/* eval_davis.py:337-342 (fuse_davis_mask) + :458-473 (memory_correct_flag).  pred_masks (Q,HW) f32 holding 0 / 1 (psalm_binarize_gather's output),
+ * pick_query (R) i32 in [0,Q) (an index outside selects an empty mask), fill (R) i32 in 0..255.  picked (R,HW) u8 = the picked masks; fused (HW) u8 = the
+ * label map, objects painted in index order (later objects overwrite earlier ones), 0 elsewhere; inter / uni (R,R) i32 = pixels in both / in either of
+ * masks i and j; nonzero (R) i32 = pixels of mask i; flag (1) i32 = 1 unless some pair i != j has 5 * inter > 2 * uni (64-bit products) -- exactly numpy's
+ * float64 `inter / uni > 0.4` (false at the ratio 2/5 itself and for two empty masks).  1 <= R <= 32, HW < 2^31.
+ * workspace: psalm_video_fuse_workspace(R) bytes (-1: bad R), 4-byte aligned; zeroed by the call itself (a memset node on `stream`). */
+long psalm_video_fuse_workspace(int R);
+int psalm_video_fuse(const float* pred_masks, const int* pick_query, const int* fill, int Q, int R, long HW, unsigned char* picked,
+                     unsigned char* fused, int* inter, int* uni, int* nonzero, int* flag, void* workspace, long workspace_bytes, void* stream);
+/* transforms.apply_segmentation of R masks (eval_davis.py:406-408: Pillow NEAREST resize, then zero padding at the bottom / right).  in (R,h,w) u8 ->
+ * out (R,Sh,Sw) u8 with out[r][y][x] = in[r][row_tab[y]][col_tab[x]]; row_tab (Sh) / col_tab (Sw) i32 are built on the host
+ * (psalm_amd/preprocess.py nearest_pad_tables), an entry < 0 marks a pad position (value 0).  row_cnt (R,Sh) i32 = non-zero pixels per output row;
+ * total_zeroed (R) i32 or NULL: += non-zero pixels per mask (integer atomics; the CALLER zeroes it). */
+int psalm_mask_resize_nearest_pad(const unsigned char* in, int R, int h, int w, const int* row_tab, const int* col_tab, int Sh, int Sw,
+                                  unsigned char* out, int* row_cnt, int* total_zeroed, void* stream);
+/* context_cluster.py:345-356 without nonzero(): pts[r][i] = (y / Sh, x / Sw) of the idx[r][i]-th non-zero pixel of masks[r] in row-major order, i.e.
+ * (masks[r].nonzero() / [Sh, Sw])[idx[r][i]].float(), bit for bit (correctly rounded fp32 division).  masks (R,Sh,Sw) u8, row_cnt (R,Sh) i32 as
+ * psalm_mask_resize_nearest_pad leaves it, idx (R,n) i32, pts (R,n,2) f32; a rank outside [0, non-zero pixels) gives (0, 0).  Sh <= 8192. */
+int psalm_mask_select_points(const unsigned char* masks, const int* row_cnt, const int* idx, int R, int Sh, int Sw, int n, float* pts, void* stream);
 
 #ifdef __cplusplus
 }

@@ -48,7 +48,7 @@ def _dt(t: torch.Tensor) -> int:
         raise PsalmHipError(f"unsupported dtype {t.dtype} (float32 / bfloat16 only)")
 
 
-ABI_VERSION = 8        # == PSALM_ABI_VERSION of include/psalm_hip.h (tests/test_0_abi.py compares the two and the built library's answer)
+ABI_VERSION = 9        # == PSALM_ABI_VERSION of include/psalm_hip.h (tests/test_0_abi.py compares the two and the built library's answer)
 
 
 class _ProfiledLib:
@@ -58,6 +58,7 @@ class _ProfiledLib:
     def __init__(self, cdll):
         object.__setattr__(self, "_cdll", cdll)
         object.__setattr__(self, "records", None)
+        object.__setattr__(self, "calls", None)          # a list: the name of every psalm_* launch is appended (no events, no change of path)
 
     def __getattr__(self, name):
         fn = getattr(self._cdll, name)
@@ -68,6 +69,8 @@ class _ProfiledLib:
 
         def call(*args):
             rec = self.records
+            if self.calls is not None:
+                self.calls.append(name)
             if _DEBUG_SYNC:
                 # PSALM_DEBUG_SYNC=1: name every launch before it is issued and synchronise after it, so that a GPU memory
                 # fault (which aborts the process asynchronously) is attributable: the last "launch" line without "ok".
@@ -91,7 +94,7 @@ class _ProfiledLib:
         return call
 
     def __setattr__(self, k, v):
-        if k == "records":
+        if k in ("records", "calls"):
             object.__setattr__(self, k, v)
         else:
             setattr(self._cdll, k, v)
@@ -1473,6 +1476,81 @@ class Ops:
                                        B, S, M, D, L, P, self._stream())
         self._check(rc, "psalm_msda_fused")
         return out
+
+
+    # ------------------------------------------------------------------ video object tracking (csrc/video.hip)
+    @staticmethod
+    def _want(t, dtype, shape, what):
+        if t.dtype != dtype or tuple(t.shape) != tuple(shape) or not t.is_contiguous():
+            raise PsalmHipError(f"{what}: contiguous {dtype} tensor of shape {tuple(shape)}, got {t.dtype} {tuple(t.shape)}")
+        return t
+
+    def video_pick(self, scores, pick_query=None, pick_score=None):
+        """scores (Q,R) f32 -> (pick_query (R) i32, pick_score (R) f32): psalm_video_pick (eval_davis.py:443-457).  The outputs may be given
+        (views of a caller-owned block)."""
+        if scores.dim() != 2 or scores.dtype != torch.float32:
+            raise PsalmHipError("video_pick: scores (Q,R) float32")
+        Q, R = scores.shape
+        pick_query = self.empty(R, dtype=torch.int32) if pick_query is None else self._want(pick_query, torch.int32, (R,), "video_pick pick_query")
+        pick_score = self.empty(R, dtype=torch.float32) if pick_score is None else self._want(pick_score, torch.float32, (R,), "video_pick pick_score")
+        self._check(self.lib.psalm_video_pick(self._p(scores), Q, R, self._p(pick_query), self._p(pick_score), self._stream()), "psalm_video_pick")
+        return pick_query, pick_score
+
+    def video_fuse(self, pred_masks, pick_query, fill, inter=None, union=None, nonzero=None, flag=None):
+        """pred_masks (Q,H,W) f32 of 0 / 1, pick_query (R) i32, fill (R) i32 -> picked (R,H,W) u8, fused (H,W) u8, inter (R,R) i32, union (R,R) i32,
+        nonzero (R) i32, flag (1) i32: psalm_video_fuse.  The four count outputs may be given (views of a caller-owned block)."""
+        if pred_masks.dim() != 3 or pred_masks.dtype != torch.float32:
+            raise PsalmHipError("video_fuse: pred_masks (Q,H,W) float32")
+        Q, Hh, Ww = pred_masks.shape
+        R = int(pick_query.numel())
+        self._want(pick_query, torch.int32, (R,), "video_fuse pick_query")
+        self._want(fill, torch.int32, (R,), "video_fuse fill")
+        inter = self.empty(R, R, dtype=torch.int32) if inter is None else self._want(inter, torch.int32, (R, R), "video_fuse inter")
+        union = self.empty(R, R, dtype=torch.int32) if union is None else self._want(union, torch.int32, (R, R), "video_fuse union")
+        nonzero = self.empty(R, dtype=torch.int32) if nonzero is None else self._want(nonzero, torch.int32, (R,), "video_fuse nonzero")
+        flag = self.empty(1, dtype=torch.int32) if flag is None else self._want(flag, torch.int32, (1,), "video_fuse flag")
+        self.lib.psalm_video_fuse_workspace.restype = c_long
+        nbytes = self.lib.psalm_video_fuse_workspace(R)
+        if nbytes < 0:
+            raise PsalmHipError(f"video_fuse: {R} objects (1..32)")
+        ws = self._stage_ws("video_fuse", nbytes)
+        picked = self.empty(R, Hh, Ww, dtype=torch.uint8)
+        fused = self.empty(Hh, Ww, dtype=torch.uint8)
+        rc = self.lib.psalm_video_fuse(self._p(pred_masks), self._p(pick_query), self._p(fill), Q, R, c_long(Hh * Ww), self._p(picked), self._p(fused),
+                                       self._p(inter), self._p(union), self._p(nonzero), self._p(flag), self._p(ws), c_long(nbytes), self._stream())
+        self._check(rc, "psalm_video_fuse")
+        return picked, fused, inter, union, nonzero, flag
+
+    def mask_resize_nearest_pad(self, masks, row_tab, col_tab, total=None):
+        """masks (R,h,w) u8, row_tab (Sh) / col_tab (Sw) i32 source indices (-1 = pad) -> (out (R,Sh,Sw) u8, row_cnt (R,Sh) i32); total (R) i32:
+        a ZEROED buffer that receives the non-zero pixels per mask.  psalm_mask_resize_nearest_pad."""
+        if masks.dim() != 3 or masks.dtype != torch.uint8:
+            raise PsalmHipError("mask_resize_nearest_pad: masks (R,h,w) uint8")
+        R, h, w = masks.shape
+        Sh, Sw = int(row_tab.numel()), int(col_tab.numel())
+        self._want(row_tab, torch.int32, (Sh,), "mask_resize_nearest_pad row_tab")
+        self._want(col_tab, torch.int32, (Sw,), "mask_resize_nearest_pad col_tab")
+        if total is not None:
+            self._want(total, torch.int32, (R,), "mask_resize_nearest_pad total")
+        out = self.empty(R, Sh, Sw, dtype=torch.uint8)
+        row_cnt = self.empty(R, Sh, dtype=torch.int32)
+        rc = self.lib.psalm_mask_resize_nearest_pad(self._p(masks), R, h, w, self._p(row_tab), self._p(col_tab), Sh, Sw, self._p(out), self._p(row_cnt),
+                                                    self._p(total), self._stream())
+        self._check(rc, "psalm_mask_resize_nearest_pad")
+        return out, row_cnt
+
+    def mask_select_points(self, masks, row_cnt, idx):
+        """masks (R,Sh,Sw) u8, row_cnt (R,Sh) i32, idx (R,n) i32 ranks in nonzero() order -> pts (R,n,2) f32 (y / Sh, x / Sw): psalm_mask_select_points."""
+        if masks.dim() != 3 or masks.dtype != torch.uint8:
+            raise PsalmHipError("mask_select_points: masks (R,Sh,Sw) uint8")
+        R, Sh, Sw = masks.shape
+        n = int(idx.shape[-1])
+        self._want(row_cnt, torch.int32, (R, Sh), "mask_select_points row_cnt")
+        self._want(idx, torch.int32, (R, n), "mask_select_points idx")
+        pts = self.empty(R, n, 2, dtype=torch.float32)
+        rc = self.lib.psalm_mask_select_points(self._p(masks), self._p(row_cnt), self._p(idx), R, Sh, Sw, n, self._p(pts), self._stream())
+        self._check(rc, "psalm_mask_select_points")
+        return pts
 
 
 _OPS: Optional[Ops] = None

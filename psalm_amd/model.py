@@ -1175,10 +1175,12 @@ class PSALM:
 
     # ======================================================================================= host preparation
     def _prepare(self, input_ids, attention_mask, images, seg_info, class_name_ids, class_name_embedding_indices, cls_indices,
-                 token_refer_id, refer_embedding_indices, region_point_sampler, video: bool = False):
+                 token_refer_id, refer_embedding_indices, region_point_sampler, video: bool = False, region_counts=None, extra_arrays=None):
         """Everything of one call that is host integer / RNG work (llava_phi.py:767-971 token splicing, region point
         sampling context_cluster.py:345-356, crop boxes LP:1418-1423), packed into ONE byte blob so that a call costs a
-        single host->device copy.  Returns (blob uint8 ndarray, layout {name: (offset, count, dtype)}, meta)."""
+        single host->device copy.  Returns (blob uint8 ndarray, layout {name: (offset, count, dtype)}, meta).
+        `region_counts` (regions per image): the caller has the region points on the DEVICE already (psalm_amd/video.py) -- no mask is read, no
+        point is sampled here and the blob carries no `region_pts`; `extra_arrays`: further named arrays to ride in the same blob."""
         cfg = self.cfg
         B, _, Hi, Wi = images.shape
         # Fast path: the SAME prompt / padding-mask tensor objects as in an earlier call, unmodified (object identity + torch's version
@@ -1204,7 +1206,10 @@ class PSALM:
         n_img = ((h5 + 2 - 3) // 2 + 1) * ((w5 + 2 - 3) // 2 + 1)                 # projector conv stride 2 (PJ:334-336)
         arrays = {}
         n_regions = None
-        if bool((input_ids == REGION_TOKEN_INDEX).any()):
+        if region_counts is not None:
+            n_regions = [int(k) for k in region_counts]
+            arrays["region_img"] = np.asarray([b for b, k in enumerate(n_regions) for _ in range(k)], np.int32)
+        elif bool((input_ids == REGION_TOKEN_INDEX).any()):
             pts, n_regions = self.region_points([(s["instances"].vp_region_masks if video else s["instances"].region_masks).tensor
                                                  for s in seg_info], region_point_sampler)                # LP:792 / LP:1664
             arrays["region_img"] = np.asarray([b for b, k in enumerate(n_regions) for _ in range(k)], np.int32)
@@ -1233,6 +1238,8 @@ class PSALM:
         post = []
         if seg_info is not None:
             post = [self._post_sizes(Hi, Wi, info, cfg.size_divisibility) for info in seg_info]
+        for name, a in (extra_arrays or {}).items():
+            arrays[name] = np.ascontiguousarray(a)
         blob, layout = self._pack(arrays)
         meta = {"B": B, "L": plan["L"], "lens": plan["lens"], "n_img": n_img, "n_cls": tuple(plan["n_cls"]),
                 "n_regions": tuple(n_regions) if n_regions is not None else None, "post": tuple(post),
@@ -1259,10 +1266,13 @@ class PSALM:
         return self._side
 
     # ======================================================================================= device forward
-    def _forward_device(self, images, dv, meta, stages: Optional[dict] = None, postprocess: bool = True, vp_images=None):
+    def _forward_device(self, images, dv, meta, stages: Optional[dict] = None, postprocess: bool = True, vp_images=None, vp_tokens=None,
+                        region_pts=None):
         """All device work of eval_seg (LP:1350-1466): only kernel launches on the current stream, no host round trip
         (so the whole call can be captured into one hipGraph).  images (B,3,H,W) fp32 on device; dv: device views of
-        the prepared blob.  Returns per-image predictor outputs (postprocess=False) or result dicts with `_pending`."""
+        the prepared blob.  Returns per-image predictor outputs (postprocess=False) or result dicts with `_pending`.
+        `vp_tokens` (B * n_img, hidden) fp32: projector tokens to pool the <region> features from, computed by an earlier call (instead of a Swin +
+        projector pass over `vp_images`); `region_pts` (R, n, 2) fp32 on the device: the region points (instead of the blob's).  Both default to off."""
         o, w, cfg = self.ops, self.w, self.cfg
         B, L, n_img = meta["B"], meta["L"], meta["n_img"]
         feats = self.swin(images)
@@ -1276,10 +1286,13 @@ class PSALM:
             side = int(math.sqrt(n_img))
             R = sum(n_regions)
             pool_tok = img_tok
-            if vp_images is not None:            # eval_video: pool from the previous frame's projector tokens (LP:1663-1670)
+            if vp_tokens is not None:            # video tracker: the memory frame's tokens, kept on the device by the step that computed them
+                pool_tok = vp_tokens
+            elif vp_images is not None:          # eval_video: pool from the previous frame's projector tokens (LP:1663-1670)
                 vf = self.swin(vp_images)
                 pool_tok, _ = self.projector(vf[3][0], B, vf[3][1], vf[3][2])
-            region_feats = o.region_pool(pool_tok, dv["region_img"], dv["region_pts"].view(R, -1, 2), side, side, n_img)
+            pts = region_pts if region_pts is not None else dv["region_pts"].view(R, -1, 2)
+            region_feats = o.region_pool(pool_tok, dv["region_img"], pts, side, side, n_img)
         # ---- the pixel decoder needs only the Swin features, the LLM only the projector tokens: run them concurrently on two
         # HIP streams (the decoder's ~150 small, latency-bound kernels fill the gaps of the LLM's large GEMMs); joined
         # before the predictor.  Captured as a fork/join inside the hipGraph in graph mode.

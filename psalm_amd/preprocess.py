@@ -116,6 +116,35 @@ def apply_segmentation(mask: np.ndarray, transforms: dict) -> np.ndarray:
     return np.pad(m, ((0, ph), (0, pw)), mode="constant", constant_values=0)
 
 
+@functools.lru_cache(maxsize=256)
+def _pil_nearest_index(in_size: int, out_size: int):
+    """Source index of every output position along one axis of Pillow's NEAREST resize (src/libImaging/Geometry.c ImagingScaleAffine, the path
+    Image.resize(..., NEAREST) takes): the source coordinate starts at scale / 2 with scale = in / out in double precision and is ADVANCED BY
+    REPEATED ADDITION (not recomputed per position), then truncated.  The running sum is reproduced term by term: its rounding decides the index
+    where a coordinate lands on an integer."""
+    scale = float(in_size) / float(out_size)
+    tab = np.empty(out_size, np.int32)
+    pos = 0.0 + scale * 0.5
+    for i in range(out_size):
+        k = -1 if pos < 0.0 else int(pos)
+        tab[i] = k if 0 <= k < in_size else -1          # (outside the source: Pillow leaves the zero fill)
+        pos += scale
+    return tab
+
+
+@functools.lru_cache(maxsize=64)
+def nearest_pad_tables(h: int, w: int, nh: int, nw: int, ph: int, pw: int):
+    """`apply_segmentation` as two source-index tables: rows (nh + ph,) and cols (nw + pw,) int32 with out[y, x] = in[rows[y], cols[x]] and -1 at
+    the pad positions (value 0) -- what psalm_mask_resize_nearest_pad reads (psalm_amd/video.py)."""
+    if (nh, nw) == (h, w):
+        rows, cols = np.arange(h, dtype=np.int32), np.arange(w, dtype=np.int32)
+    else:
+        rows, cols = _pil_nearest_index(h, nh), _pil_nearest_index(w, nw)
+    rows = np.concatenate([rows, np.full(ph, -1, np.int32)])
+    cols = np.concatenate([cols, np.full(pw, -1, np.int32)])
+    return np.ascontiguousarray(rows), np.ascontiguousarray(cols)
+
+
 def region_masks_from_annotations(annotations, transforms: dict, region_mask_type=None, rng=None):
     """coco_instance_mapper.py:233-252 for the non-crowd annotations of one image.  Returns (region_masks (k, S, S) uint8 array, indices of the
     annotations that received a prompt -- the `filter_annos` of the reference).  `region_mask_type`: the list of prompt kinds to draw from

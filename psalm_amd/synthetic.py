@@ -16,6 +16,7 @@ from __future__ import annotations
 import math
 from typing import Dict, List, Optional
 
+import numpy as np
 import torch
 
 from .config import (CLS_TOKEN_INDEX, IMAGE_TOKEN_INDEX, REFER_TOKEN_INDEX, REGION_TOKEN_INDEX,
@@ -398,3 +399,51 @@ def fix_indices(inp):
     if "refer_embedding_indices" in inp:
         inp["refer_embedding_indices"] = (ids == PR.REFER_TOKEN_INDEX).to(torch.int64)
     return inp
+
+
+# ---- video object tracking (psalm_amd/video.py): the per-frame inputs of a DAVIS-style clip
+def video_clip_inputs(cfg, frames, n_objects, size=96, orig=(60, 80), seed=4, clip="clip0", radius=None):
+    """`frames` keyword dicts for `VideoTracker.step(**d)` / `eval_video(**d)` (batch 1), as the reference's DAVIS dataset + collator hand them to
+    eval_davis.py:421-428: a frame of original size `orig` resized and padded into the (size, size) canvas the way ImagePreprocessor does
+    (`seg_info[0]["transforms"]`, `padding_mask`, `height` / `width`), the clip's FIRST frame as `vp_images` with one disc per object as
+    `vp_region_masks` (after apply_segmentation) and `vp_fill_number` 1..n_objects, one prompt with n_objects <region> tokens."""
+    from .preprocess import apply_segmentation
+    g = torch.Generator(device="cpu")
+    g.manual_seed(3000 + seed)
+    V = cfg.vocab_size
+    h, w = orig
+    nh, nw = resized_box(h, w, size)
+    tr = {"resize": (h, w, nh, nw), "pad": (size - nh, size - nw)}
+
+    def txt(n):
+        return torch.randint(5, V, (n,), generator=g).tolist()
+
+    def frame():
+        img = torch.randn(1, 3, size, size, generator=g, dtype=torch.float32)
+        img[:, :, nh:, :] = 0
+        img[:, :, :, nw:] = 0
+        return img
+
+    ids = txt(3) + [IMAGE_TOKEN_INDEX] + txt(2) + [REGION_TOKEN_INDEX] * n_objects + txt(2) + [SEG_TOKEN_INDEX] + txt(1)
+    input_ids = torch.tensor([ids], dtype=torch.int64)
+    first = frame()
+    rad = radius or max(2, min(h, w) // 8)
+    discs = []
+    for j in range(n_objects):
+        cy = int(torch.randint(rad, h - rad, (1,), generator=g))
+        cx = int(torch.randint(rad, w - rad, (1,), generator=g))
+        yy, xx = torch.meshgrid(torch.arange(h), torch.arange(w), indexing="ij")
+        discs.append((((yy - cy) ** 2 + (xx - cx) ** 2) <= rad * rad).numpy().astype("uint8"))
+    vp = torch.from_numpy(np.stack([apply_segmentation(d, tr) for d in discs]))
+    pm = torch.zeros(size, size, dtype=torch.bool)
+    pm[nh:, :] = True
+    pm[:, nw:] = True
+    out = []
+    for t in range(frames):
+        inst = RegionInstances(vp.clone(), vp.clone().float(), vp.clone())
+        inst.vp_fill_number = torch.arange(1, n_objects + 1, dtype=torch.int64)
+        info = {"padding_mask": pm.clone(), "height": h, "width": w, "transforms": dict(tr), "instances": inst,
+                "file_name": f"DAVIS/JPEGImages/480p/{clip}/{t:05d}.jpg"}
+        out.append({"input_ids": input_ids.clone(), "attention_mask": torch.ones_like(input_ids, dtype=torch.bool),
+                    "images": first.clone() if t == 0 else frame(), "vp_images": first.clone(), "seg_info": [info], "labels": input_ids.clone()})
+    return out
