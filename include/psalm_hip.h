@@ -33,8 +33,10 @@ const char* psalm_last_error(void);
  *    psalm_predictor_forward (r06).
  * 8: image sessions: psalm_causal_attention_f32_prefix[_split] (+ _workspace), psalm_phi_prefix_kv_store, the stage-level psalm_phi_prefix /
  *    psalm_phi_suffix (+ their _workspace / _cache_bytes functions).
- * 9: video object tracking: psalm_video_pick, psalm_video_fuse (+ _workspace), psalm_mask_resize_nearest_pad, psalm_mask_select_points. */
-#define PSALM_ABI_VERSION 9
+ * 9: video object tracking: psalm_video_pick, psalm_video_fuse (+ _workspace), psalm_mask_resize_nearest_pad, psalm_mask_select_points.
+ * 10: grouped image sessions: psalm_prefix_ref, psalm_causal_attention_f32_prefix_grouped[_split] (+ _workspace), the stage-level
+ *    psalm_phi_suffix_grouped (+ _workspace). */
+#define PSALM_ABI_VERSION 10
 int psalm_abi_version(void);
 const char* psalm_backend(void); /* "hip-gfx950" */
 
@@ -262,6 +264,31 @@ int psalm_causal_attention_f32_prefix_split(const float* qkv, long ld, int q_off
                                             const float* split_inv, const float* cos_table, const float* sin_table,
                                             const unsigned char* key_mask, void* workspace, int N, int S, int P, int heads, int head_dim,
                                             int rot, void* stream);
+/* Grouped prefix form (PSALM.segment_many: prompts of SEVERAL image sessions in one launch).  The arguments are those of the prefix entries, but
+ * `k_cache, v_cache, ldv, P` become a DEVICE table `refs` of N entries: prompt n's sequence is [refs[n].P prefix rows of its own cache | S suffix
+ * rows], suffix row s sits at position refs[n].P + s, and cos / sin hold >= max_n refs[n].P + S rows.  Entries may repeat (prompts of one session
+ * share a cache).  Every entry obeys the rules of the ungrouped arguments: P >= 1, K cache (heads, ceil32(P), 64) with zero padding rows, V rows of
+ * ldv >= heads * 64 floats, ldv % 4 == 0, both 16-byte aligned, P * ldv * 4 below 2 GiB.  The table is never read on the host: P_max >= every
+ * refs[n].P is what the host checks (P_max >= 1, the 2 GiB bounds at the smallest legal ldv) -- the entries themselves are the caller's word
+ * (psalm_amd/hip_ops.py checks the host copy it uploads).  A block computes, word for word, what the ungrouped entry computes when called with
+ * that prompt's cache and P and the same S: same bits (tests/test_16_grouped_prefix_attention.py). */
+typedef struct {
+    const float* k_cache;
+    const float* v_cache;
+    long ldv;
+    int P;
+    int pad;
+} psalm_prefix_ref; /* 32 bytes; tables are 16-byte aligned */
+long psalm_causal_attention_f32_prefix_grouped_workspace(int N, int S, int heads);
+int psalm_causal_attention_f32_prefix_grouped(const float* qkv, long ld, int q_off, int k_off, int v_off, const psalm_prefix_ref* refs, int P_max,
+                                              float* out, long ldo, int o_off, const float* cos_table, const float* sin_table,
+                                              const unsigned char* key_mask, void* workspace, int N, int S, int heads, int head_dim, int rot,
+                                              void* stream);
+int psalm_causal_attention_f32_prefix_grouped_split(const float* qkv, long ld, int q_off, int k_off, int v_off, const psalm_prefix_ref* refs,
+                                                    int P_max, void* split_out, long ld_split, int split_kp, int split_col_off,
+                                                    const float* split_inv, const float* cos_table, const float* sin_table,
+                                                    const unsigned char* key_mask, void* workspace, int N, int S, int heads, int head_dim,
+                                                    int rot, void* stream);
 /* Producer of one layer's prefix cache from the [k | v | q | ...] buffer of the P prefix rows (positions 0 .. P-1): k_cache <- RoPE(k) in the
  * (heads, ceil32(P), 64) layout (padding rows zero), v_cache row t <- v of row t (row stride ldv floats). */
 int psalm_phi_prefix_kv_store(const float* qkv, long ld, int k_off, int v_off, const float* cos_table, const float* sin_table, float* k_cache,
@@ -492,6 +519,16 @@ long psalm_phi_suffix_workspace(const psalm_phi_desc* d, int N, int S);
 int psalm_phi_suffix(const psalm_phi_desc* d, const float* embeds, const unsigned char* key_mask, const float* cos_table, const float* sin_table,
                      int N, int S, int P, const void* cache, long cache_bytes, float* hidden_out, void* workspace, long workspace_bytes,
                      void* gemm_workspace, long gemm_workspace_bytes, void* stream);
+/* psalm_phi_suffix_grouped (PSALM.segment_many): psalm_phi_suffix whose `P, cache, cache_bytes` become a device table of (num_layers, N)
+ *   psalm_prefix_ref entries -- row i holds layer i's cache blocks of every prompt's session -- plus P_max >= every entry's P; cos / sin hold
+ *   >= P_max + S rows.  Launch sequence, fusions and workspace (psalm_phi_suffix_grouped_workspace = psalm_phi_suffix_workspace) are unchanged.
+ * The scale contract above applies as written: the row-scale maximum now runs over the suffix rows of ALL prompts of the call, and a maximum over
+ *   more rows is never smaller, so the (still unenforced) bound covers every session's prefix V rows at least as far as a call on that session
+ *   alone would. */
+long psalm_phi_suffix_grouped_workspace(const psalm_phi_desc* d, int N, int S);
+int psalm_phi_suffix_grouped(const psalm_phi_desc* d, const float* embeds, const unsigned char* key_mask, const float* cos_table,
+                             const float* sin_table, int N, int S, const psalm_prefix_ref* refs, int P_max, float* hidden_out, void* workspace,
+                             long workspace_bytes, void* gemm_workspace, long gemm_workspace_bytes, void* stream);
 
 /* psalm_swin_forward: SwinTransformer.forward (swin_trans.py:608-633; blocks :194-253, window attention :117-149, patch merging :266-296, patch
  * embedding :427-443), precision "f16x3", 12 x 12 windows, head dim 32.  GEMM weights in split-f16 form (`*_w` rows of 2*ceil64(K) f16, `*_ws`

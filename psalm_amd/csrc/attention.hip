@@ -11,6 +11,7 @@
 //   psalm_attn_mask         bilinear resize of mask logits + (sigmoid < 0.5) -> u8 mask + all-masked row flags
 //                           (mask2former_transformer_decoder.py:754-759)
 #include "common.h"
+#include "psalm_hip.h"
 #include <cstdlib>
 
 // ============================================================================================ Swin window attention
@@ -687,13 +688,19 @@ __global__ void __launch_bounds__(64 * NW) causal_attention_f32_mfma_kernel(cons
 // CU), each keeping a private online-softmax state that is merged through LDS at the end.  No tile is shared between wavefronts, so K
 // and V^T fragments are read straight from global / L2 (K rows and V rows are contiguous 128 / 256 B per lane group); RoPE, the 1/sqrt(d)
 // scale and the padded key mask come from a small pre-pass (phi_rope_prep_f32_kernel) into the caller's workspace.
+// GR (grouped prefix form, psalm_causal_attention_f32_prefix_grouped): sequence b sits behind a prefix of its own, refs[b].P rows long -- its row t
+// takes row refs[b].P + t of the tables (the ungrouped prefix form passes tables shifted by its one P instead).
+template <bool GR = false>
 __global__ void __launch_bounds__(256) phi_rope_prep_f32_kernel(const float* __restrict__ base, long ld, int q_off, int k_off,
                                                                 const float* __restrict__ cosT, const float* __restrict__ sinT,
                                                                 const unsigned char* __restrict__ key_mask, float* __restrict__ Qr,
                                                                 float* __restrict__ Kr, unsigned char* __restrict__ Mk,
-                                                                unsigned char* __restrict__ Tk, int L, int Lp, int heads, float scale) {
+                                                                unsigned char* __restrict__ Tk, int L, int Lp, int heads, float scale,
+                                                                const psalm_prefix_ref* __restrict__ refs) {
     constexpr int HD = 64, ROT = 32, half = 16;
     const int h = blockIdx.y, b = blockIdx.z;
+    long pos0 = 0;                                       // (block-uniform)
+    if constexpr (GR) pos0 = refs[b].P;
     const int t = blockIdx.x * 32 + (threadIdx.x >> 3), c0 = (threadIdx.x & 7) * 8;     // token, 8-wide head-dim chunk
     if (t >= Lp) return;
     float* qd = Qr + (((long)b * heads + h) * Lp + t) * HD + c0;
@@ -723,8 +730,8 @@ __global__ void __launch_bounds__(256) phi_rope_prep_f32_kernel(const float* __r
             const int oc = c0 < half ? c0 + half : c0 - half;
             ld8(p + q_off + h * HD + oc, qo);
             ld8(p + k_off + h * HD + oc, ko);
-            ld8(cosT + (long)t * ROT + c0, cs);
-            ld8(sinT + (long)t * ROT + c0, sn);
+            ld8(cosT + (pos0 + t) * ROT + c0, cs);
+            ld8(sinT + (pos0 + t) * ROT + c0, sn);
 #pragma unroll
             for (int i = 0; i < 8; ++i) {
                 q[i] = q[i] * cs[i] + (c0 < half ? -qo[i] : qo[i]) * sn[i];
@@ -958,8 +965,8 @@ static int causal_attention_f32_impl(const float* qkv, long ld, int q_off, int k
     PSALM_CHECK_ARG(((long)L - 1) * ld * 4 + 256 < 0x7fffffffL, "psalm_causal_attention_f32: L * ld * 4 must stay below 2 GiB (buffer-descriptor fetches)");
     const float scale = 1.0f / sqrtf((float)head_dim);
     hipStream_t s = (hipStream_t)stream;
-    hipLaunchKernelGGL(phi_rope_prep_f32_kernel, dim3(Lp / 32, heads, B), dim3(256), 0, s, qkv, ld, q_off, k_off, cos_table, sin_table, key_mask,
-                       Qr, Kr, Mk, Tk, L, Lp, heads, scale);
+    hipLaunchKernelGGL(phi_rope_prep_f32_kernel<false>, dim3(Lp / 32, heads, B), dim3(256), 0, s, qkv, ld, q_off, k_off, cos_table, sin_table, key_mask,
+                       Qr, Kr, Mk, Tk, L, Lp, heads, scale, (const psalm_prefix_ref*)nullptr);
     const int pair = 1;                                                   // balanced pairs of query tiles per block (r02n; the one-tile form stays in the kernel)
     const int nqt = Lp / 32;
     const dim3 grid(pair ? (nqt + 1) / 2 : nqt, heads, B);
@@ -1046,18 +1053,23 @@ extern "C" int psalm_phi_prefix_kv_store(const float* qkv, long ld, int k_off, i
     PSALM_LAUNCH_END("psalm_phi_prefix_kv_store");
 }
 
-template <bool SO>
+// GR (grouped form: prompts of SEVERAL sessions in one launch): prompt b's cache, row stride and prefix length come from refs[b] instead of the
+// arguments -- one block-uniform 32-byte entry, read once, from which the two prefix descriptors are built.  Nothing else differs: a block's
+// tile list, wave dealing, tile body and merge are those of the ungrouped kernel called with that prompt's cache and P (same bits,
+// tests/test_16_grouped_prefix_attention.py).
+template <bool SO, bool GR = false>
 __global__ void __launch_bounds__(256) PSALM_WAVES_PER_EU(3)
 causal_attention_f32_prefix_kernel(const float* __restrict__ Qr, const float* __restrict__ Kr, const unsigned char* __restrict__ Mk,
                                    const unsigned char* __restrict__ Tk, const float* __restrict__ base, long ld, int v_off,
-                                   const float* __restrict__ Kc, const float* __restrict__ Vc, long ldv, int P, int Pp, float* out, long ldo,
-                                   int o_off, int S, int Sp, int heads, const float* __restrict__ so_inv, int so_kp, int xcd_heads) {
+                                   const float* __restrict__ Kc_, const float* __restrict__ Vc_, long ldv_, int P_, int Pp_, float* out, long ldo,
+                                   int o_off, int S, int Sp, int heads, const float* __restrict__ so_inv, int so_kp, int xcd_heads,
+                                   const psalm_prefix_ref* __restrict__ refs) {
     typedef float f32x16 __attribute__((ext_vector_type(16)));
     constexpr int HD = 64, OS = HD + 4;
     __shared__ __attribute__((aligned(16))) float Os[4][32 * OS];         // per-wave O (q-major) for the merge
     __shared__ float Ml[4][2][32];                                        // per-wave (m, l) per query
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, n32 = lane & 31, hi = lane >> 5;
-    const int nqt = Sp / 32, npt = Pp / 32;
+    const int nqt = Sp / 32;
     int bx = blockIdx.x, h = blockIdx.y, b = blockIdx.z;                   // XCD x runs the (prompt, head) pairs x, x + 8, ...: see causal_attention_f32_splitk_kernel
     if (xcd_heads) {
         const int lin = (int)(blockIdx.x + gridDim.x * (blockIdx.y + gridDim.y * blockIdx.z));
@@ -1066,6 +1078,19 @@ causal_attention_f32_prefix_kernel(const float* __restrict__ Qr, const float* __
         h = hb % heads;
         b = hb / heads;
     }
+    const float* Kc = Kc_;
+    const float* Vc = Vc_;
+    long ldv = ldv_;
+    int P = P_, Pp = Pp_;
+    if constexpr (GR) {                                                   // (b is block-uniform: scalar loads)
+        const psalm_prefix_ref r = refs[b];
+        Kc = r.k_cache;
+        Vc = r.v_cache;
+        ldv = r.ldv;
+        P = r.P;
+        Pp = (P + 31) / 32 * 32;
+    }
+    const int npt = Pp / 32;
     const long bh = (long)b * heads + h;
     const int qt = nqt - 1 - bx;                                          // heaviest (last) query tile first
     const int qi = qt * 32 + n32;                                         // this lane's query column (row qi < Sp of Qr)
@@ -1232,18 +1257,26 @@ extern "C" long psalm_causal_attention_f32_prefix_workspace(int N, int S, int he
     return psalm_causal_attention_f32_workspace(N, S, heads);              // RoPE'd Q / K of the suffix rows + their padded key mask
 }
 
+// refs == nullptr: the one prefix (k_cache, v_cache, ldv, P) of all N prompts; else the grouped form: refs (N) entries on the DEVICE (never read
+// here), P = the largest prefix length of the table
 static int causal_attention_f32_prefix_impl(const float* qkv, long ld, int q_off, int k_off, int v_off, const float* k_cache, const float* v_cache,
-                                            long ldv, void* out, long ldo, int o_off, const float* cos_table, const float* sin_table,
-                                            const unsigned char* key_mask, void* workspace, int N, int S, int P, int heads, int head_dim, int rot,
-                                            void* stream, const float* so_inv, int so_kp, const char* name) {
+                                            long ldv, const psalm_prefix_ref* refs, void* out, long ldo, int o_off, const float* cos_table,
+                                            const float* sin_table, const unsigned char* key_mask, void* workspace, int N, int S, int P, int heads,
+                                            int head_dim, int rot, void* stream, const float* so_inv, int so_kp, const char* name) {
     PSALM_CHECK_ARG(head_dim == 64 && rot == 32, "psalm_causal_attention_f32_prefix: head_dim 64, rotary dim 32 (Phi-1.5)");
     PSALM_CHECK_ARG(ld % 4 == 0 && q_off % 4 == 0 && k_off % 4 == 0 && v_off % 4 == 0 && (uintptr_t)qkv % 16 == 0 &&
                         (uintptr_t)out % 16 == 0 && workspace && (uintptr_t)workspace % 16 == 0 &&
                         (so_inv ? (ldo % 8 == 0 && o_off % 8 == 0 && so_kp % 8 == 0) : (ldo % 4 == 0 && o_off % 4 == 0)),
                     "psalm_causal_attention_f32_prefix: 16-byte aligned rows / offsets and a workspace");
-    PSALM_CHECK_ARG(P >= 1 && k_cache && v_cache && (uintptr_t)k_cache % 16 == 0 && (uintptr_t)v_cache % 16 == 0 && ldv % 4 == 0 &&
-                        ldv >= (long)heads * 64 && key_mask && cos_table && sin_table,
-                    "psalm_causal_attention_f32_prefix: a prefix of >= 1 rows: K cache (heads, ceil32(P), 64), V cache rows of >= heads * 64 floats, 16-byte aligned");
+    if (refs) {
+        PSALM_CHECK_ARG(P >= 1 && (uintptr_t)refs % 16 == 0 && heads >= 1 && key_mask && cos_table && sin_table,
+                        "psalm_causal_attention_f32_prefix_grouped: a 16-byte aligned table of N entries, P_max >= 1");
+        ldv = (long)heads * 64;                                           // the smallest row stride an entry may carry (bounds below)
+    } else {
+        PSALM_CHECK_ARG(P >= 1 && k_cache && v_cache && (uintptr_t)k_cache % 16 == 0 && (uintptr_t)v_cache % 16 == 0 && ldv % 4 == 0 &&
+                            ldv >= (long)heads * 64 && key_mask && cos_table && sin_table,
+                        "psalm_causal_attention_f32_prefix: a prefix of >= 1 rows: K cache (heads, ceil32(P), 64), V cache rows of >= heads * 64 floats, 16-byte aligned");
+    }
     if (N == 0 || S == 0) return 0;
     const int Sp = (S + 31) / 32 * 32, Pp = (P + 31) / 32 * 32;
     PSALM_CHECK_ARG(((long)S - 1) * ld * 4 + 256 < 0x7fffffffL && ((long)P - 1) * ldv * 4 + 256 < 0x7fffffffL && (long)Pp * 64 * 4 < 0x7fffffffL,
@@ -1254,26 +1287,41 @@ static int causal_attention_f32_prefix_impl(const float* qkv, long ld, int q_off
     unsigned char* Tk = Mk + (long)N * Sp;
     const float scale = 1.0f / sqrtf((float)head_dim);
     hipStream_t s = (hipStream_t)stream;
-    // the suffix rows sit at the absolute positions P + s: the same pre-pass as the prefill's, on tables that start at row P
-    hipLaunchKernelGGL(phi_rope_prep_f32_kernel, dim3(Sp / 32, heads, N), dim3(256), 0, s, qkv, ld, q_off, k_off, cos_table + (long)P * rot,
-                       sin_table + (long)P * rot, key_mask, Qr, Kr, Mk, Tk, S, Sp, heads, scale);
     const dim3 grid(Sp / 32, heads, N);
     const int xcd_heads = ((heads * N) % 8 == 0 && psalm_get_tuning(PSALM_TUNE_ATTN_XCD_HEADS)) ? 1 : 0;
+    if (refs) {
+        // suffix row s of prompt n sits at position refs[n].P + s: the pre-pass takes the offset from the table, one launch for all prompts
+        hipLaunchKernelGGL(phi_rope_prep_f32_kernel<true>, dim3(Sp / 32, heads, N), dim3(256), 0, s, qkv, ld, q_off, k_off, cos_table, sin_table,
+                           key_mask, Qr, Kr, Mk, Tk, S, Sp, heads, scale, refs);
+        if (so_inv)
+            hipLaunchKernelGGL((causal_attention_f32_prefix_kernel<true, true>), grid, dim3(256), 0, s, (const float*)Qr, (const float*)Kr,
+                               (const unsigned char*)Mk, (const unsigned char*)Tk, qkv, ld, v_off, (const float*)nullptr, (const float*)nullptr, 0L, 0, 0,
+                               (float*)out, ldo, o_off, S, Sp, heads, so_inv, so_kp, xcd_heads, refs);
+        else
+            hipLaunchKernelGGL((causal_attention_f32_prefix_kernel<false, true>), grid, dim3(256), 0, s, (const float*)Qr, (const float*)Kr,
+                               (const unsigned char*)Mk, (const unsigned char*)Tk, qkv, ld, v_off, (const float*)nullptr, (const float*)nullptr, 0L, 0, 0,
+                               (float*)out, ldo, o_off, S, Sp, heads, (const float*)nullptr, 0, xcd_heads, refs);
+        PSALM_LAUNCH_END(name);
+    }
+    // the suffix rows sit at the absolute positions P + s: the same pre-pass as the prefill's, on tables that start at row P
+    hipLaunchKernelGGL(phi_rope_prep_f32_kernel<false>, dim3(Sp / 32, heads, N), dim3(256), 0, s, qkv, ld, q_off, k_off, cos_table + (long)P * rot,
+                       sin_table + (long)P * rot, key_mask, Qr, Kr, Mk, Tk, S, Sp, heads, scale, (const psalm_prefix_ref*)nullptr);
     if (so_inv)
-        hipLaunchKernelGGL(causal_attention_f32_prefix_kernel<true>, grid, dim3(256), 0, s, (const float*)Qr, (const float*)Kr, (const unsigned char*)Mk,
-                           (const unsigned char*)Tk, qkv, ld, v_off, k_cache, v_cache, ldv, P, Pp, (float*)out, ldo, o_off, S, Sp, heads, so_inv, so_kp, xcd_heads);
+        hipLaunchKernelGGL((causal_attention_f32_prefix_kernel<true, false>), grid, dim3(256), 0, s, (const float*)Qr, (const float*)Kr, (const unsigned char*)Mk,
+                           (const unsigned char*)Tk, qkv, ld, v_off, k_cache, v_cache, ldv, P, Pp, (float*)out, ldo, o_off, S, Sp, heads, so_inv, so_kp, xcd_heads,
+                           (const psalm_prefix_ref*)nullptr);
     else
-        hipLaunchKernelGGL(causal_attention_f32_prefix_kernel<false>, grid, dim3(256), 0, s, (const float*)Qr, (const float*)Kr, (const unsigned char*)Mk,
+        hipLaunchKernelGGL((causal_attention_f32_prefix_kernel<false, false>), grid, dim3(256), 0, s, (const float*)Qr, (const float*)Kr, (const unsigned char*)Mk,
                            (const unsigned char*)Tk, qkv, ld, v_off, k_cache, v_cache, ldv, P, Pp, (float*)out, ldo, o_off, S, Sp, heads,
-                           (const float*)nullptr, 0, xcd_heads);
+                           (const float*)nullptr, 0, xcd_heads, (const psalm_prefix_ref*)nullptr);
     PSALM_LAUNCH_END(name);
 }
 extern "C" int psalm_causal_attention_f32_prefix(const float* qkv, long ld, int q_off, int k_off, int v_off, const float* k_cache,
                                                  const float* v_cache, long ldv, float* out, long ldo, int o_off, const float* cos_table,
                                                  const float* sin_table, const unsigned char* key_mask, void* workspace, int N, int S, int P,
                                                  int heads, int head_dim, int rot, void* stream) {
-    return causal_attention_f32_prefix_impl(qkv, ld, q_off, k_off, v_off, k_cache, v_cache, ldv, out, ldo, o_off, cos_table, sin_table, key_mask,
-                                            workspace, N, S, P, heads, head_dim, rot, stream, nullptr, 0, "psalm_causal_attention_f32_prefix");
+    return causal_attention_f32_prefix_impl(qkv, ld, q_off, k_off, v_off, k_cache, v_cache, ldv, nullptr, out, ldo, o_off, cos_table, sin_table,
+                                            key_mask, workspace, N, S, P, heads, head_dim, rot, stream, nullptr, 0, "psalm_causal_attention_f32_prefix");
 }
 extern "C" int psalm_causal_attention_f32_prefix_split(const float* qkv, long ld, int q_off, int k_off, int v_off, const float* k_cache,
                                                        const float* v_cache, long ldv, void* split_out, long ld_split, int split_kp,
@@ -1282,9 +1330,36 @@ extern "C" int psalm_causal_attention_f32_prefix_split(const float* qkv, long ld
                                                        int head_dim, int rot, void* stream) {
     PSALM_CHECK_ARG(split_out && split_inv && ld_split >= 2L * split_kp && split_col_off + heads * 64 <= split_kp,
                     "psalm_causal_attention_f32_prefix_split: split buffer rows of >= 2*split_kp f16 and the row scales");
-    return causal_attention_f32_prefix_impl(qkv, ld, q_off, k_off, v_off, k_cache, v_cache, ldv, split_out, ld_split, split_col_off, cos_table,
-                                            sin_table, key_mask, workspace, N, S, P, heads, head_dim, rot, stream, split_inv, split_kp,
+    return causal_attention_f32_prefix_impl(qkv, ld, q_off, k_off, v_off, k_cache, v_cache, ldv, nullptr, split_out, ld_split, split_col_off,
+                                            cos_table, sin_table, key_mask, workspace, N, S, P, heads, head_dim, rot, stream, split_inv, split_kp,
                                             "psalm_causal_attention_f32_prefix_split");
+}
+
+// ---- grouped prefix form (PSALM.segment_many: prompts of several image sessions in one pass): prompt n names its own cache and prefix length
+// through refs[n] (device memory, one entry per prompt, never read on the host); P_max >= every refs[n].P serves the checks above.
+extern "C" long psalm_causal_attention_f32_prefix_grouped_workspace(int N, int S, int heads) {
+    return psalm_causal_attention_f32_prefix_workspace(N, S, heads);
+}
+extern "C" int psalm_causal_attention_f32_prefix_grouped(const float* qkv, long ld, int q_off, int k_off, int v_off, const psalm_prefix_ref* refs,
+                                                         int P_max, float* out, long ldo, int o_off, const float* cos_table, const float* sin_table,
+                                                         const unsigned char* key_mask, void* workspace, int N, int S, int heads, int head_dim,
+                                                         int rot, void* stream) {
+    PSALM_CHECK_ARG(refs && P_max >= 1, "psalm_causal_attention_f32_prefix_grouped: null table / P_max < 1");
+    return causal_attention_f32_prefix_impl(qkv, ld, q_off, k_off, v_off, nullptr, nullptr, 0, refs, out, ldo, o_off, cos_table, sin_table, key_mask,
+                                            workspace, N, S, P_max, heads, head_dim, rot, stream, nullptr, 0,
+                                            "psalm_causal_attention_f32_prefix_grouped");
+}
+extern "C" int psalm_causal_attention_f32_prefix_grouped_split(const float* qkv, long ld, int q_off, int k_off, int v_off,
+                                                               const psalm_prefix_ref* refs, int P_max, void* split_out, long ld_split,
+                                                               int split_kp, int split_col_off, const float* split_inv, const float* cos_table,
+                                                               const float* sin_table, const unsigned char* key_mask, void* workspace, int N,
+                                                               int S, int heads, int head_dim, int rot, void* stream) {
+    PSALM_CHECK_ARG(refs && P_max >= 1, "psalm_causal_attention_f32_prefix_grouped_split: null table / P_max < 1");
+    PSALM_CHECK_ARG(split_out && split_inv && ld_split >= 2L * split_kp && split_col_off + heads * 64 <= split_kp,
+                    "psalm_causal_attention_f32_prefix_grouped_split: split buffer rows of >= 2*split_kp f16 and the row scales");
+    return causal_attention_f32_prefix_impl(qkv, ld, q_off, k_off, v_off, nullptr, nullptr, 0, refs, split_out, ld_split, split_col_off, cos_table,
+                                            sin_table, key_mask, workspace, N, S, P_max, heads, head_dim, rot, stream, split_inv, split_kp,
+                                            "psalm_causal_attention_f32_prefix_grouped_split");
 }
 
 extern "C" int psalm_causal_attention(const void* qkv, int dtype, long ld, int q_off, int k_off, int v_off, void* out, long ldo,

@@ -148,11 +148,13 @@ extern "C" long psalm_phi_suffix_workspace(const psalm_phi_desc* d, int N, int S
 // suffix = false: the P = L prefix rows (B = 1), cache written; suffix = true: B * L suffix rows behind a prefix of P rows, cache read
 static int phi_session_pass(const psalm_phi_desc* d, bool suffix, const float* embeds, const unsigned char* key_mask, const float* cos_table,
                             const float* sin_table, int B, int L, int P, char* cache, long cache_bytes, float* hidden_out, void* workspace,
-                            long workspace_bytes, void* gemm_workspace, long gemm_workspace_bytes, void* stream) {
+                            long workspace_bytes, void* gemm_workspace, long gemm_workspace_bytes, void* stream,
+                            const psalm_prefix_ref* refs = nullptr) {
+    // refs (suffix only): the grouped form -- (num_layers, B) device entries name each prompt's cache, P is the largest prefix length, no `cache`
     const PhiLayout lo = phi_layout(d, B, L);
     const PhiCacheLayout cl = phi_cache_layout(d, P);
     PSALM_CHECK_ARG(workspace_bytes >= lo.total && (uintptr_t)workspace % 256 == 0, "psalm_phi_prefix / _suffix: workspace of the _workspace() function's bytes, 256-byte aligned");
-    PSALM_CHECK_ARG(cache_bytes >= cl.stride * d->num_layers && (uintptr_t)cache % 256 == 0, "psalm_phi_prefix / _suffix: cache of psalm_phi_prefix_cache_bytes() bytes, 256-byte aligned");
+    PSALM_CHECK_ARG(refs || (cache_bytes >= cl.stride * d->num_layers && (uintptr_t)cache % 256 == 0), "psalm_phi_prefix / _suffix: cache of psalm_phi_prefix_cache_bytes() bytes, 256-byte aligned");
     char* ws = (char*)workspace;
     const int M = B * L, H = d->hidden, I = d->intermediate, Kp = lo.Kp, K2 = H + I;
     float* x[2] = {(float*)(ws + lo.x0), (float*)(ws + lo.x1)};
@@ -172,8 +174,8 @@ static int phi_session_pass(const psalm_phi_desc* d, bool suffix, const float* e
         const psalm_phi_layer* ly = &d->layers[i];
         const bool last = i == d->num_layers - 1;
         PSALM_CHECK_ARG(ly->w1 && ly->w1_scale && ly->b1 && ly->w2 && ly->w2_scale && ly->b2 && ly->bnd, "psalm_phi_prefix / _suffix: layer weights missing");
-        float* kc = (float*)(cache + cl.stride * i);
-        float* vc = (float*)(cache + cl.stride * i + cl.k_bytes);
+        float* kc = refs ? nullptr : (float*)(cache + cl.stride * i);
+        float* vc = refs ? nullptr : (float*)(cache + cl.stride * i + cl.k_bytes);
         rc = psalm_gemm_x3_split(h, 2L * Kp, hinv, ly->w1, 2L * Kp, ly->w1_scale, Kp, ly->b1, big, 3L * H, M, 3 * H + I, /*gelu_new*/ 3, 3 * H, a2,
                                  2L * K2, K2, H, 3 * H, ly->paired, inv2, ly->bnd, 1, gemm_workspace, gemm_workspace_bytes, stream);
         if (rc) return rc;
@@ -183,6 +185,9 @@ static int phi_session_pass(const psalm_phi_desc* d, bool suffix, const float* e
             if (last) break;                                              // nothing downstream reads the prefix rows' last hidden states
             rc = psalm_causal_attention_f32_split(big, 3L * H, 2 * H, 0, H, a2, 2L * K2, K2, 0, inv2, cos_table, sin_table, key_mask, attn, B, L, d->heads,
                                                   d->head_dim, d->rot, stream);
+        } else if (refs) {
+            rc = psalm_causal_attention_f32_prefix_grouped_split(big, 3L * H, 2 * H, 0, H, refs + (long)i * B, P, a2, 2L * K2, K2, 0, inv2, cos_table,
+                                                                 sin_table, key_mask, attn, B, L, d->heads, d->head_dim, d->rot, stream);
         } else {
             rc = psalm_causal_attention_f32_prefix_split(big, 3L * H, 2 * H, 0, H, kc, vc, H, a2, 2L * K2, K2, 0, inv2, cos_table, sin_table, key_mask, attn,
                                                          B, L, P, d->heads, d->head_dim, d->rot, stream);
@@ -229,6 +234,19 @@ extern "C" int psalm_phi_suffix(const psalm_phi_desc* d, const float* embeds, co
                     "psalm_phi_suffix: null argument");
     return phi_session_pass(d, true, embeds, key_mask, cos_table, sin_table, N, S, P, (char*)cache, cache_bytes, hidden_out, workspace,
                             workspace_bytes, gemm_workspace, gemm_workspace_bytes, stream);
+}
+
+extern "C" long psalm_phi_suffix_grouped_workspace(const psalm_phi_desc* d, int N, int S) { return psalm_phi_suffix_workspace(d, N, S); }
+
+extern "C" int psalm_phi_suffix_grouped(const psalm_phi_desc* d, const float* embeds, const unsigned char* key_mask, const float* cos_table,
+                                        const float* sin_table, int N, int S, const psalm_prefix_ref* refs, int P_max, float* hidden_out,
+                                        void* workspace, long workspace_bytes, void* gemm_workspace, long gemm_workspace_bytes, void* stream) {
+    if (phi_check(d) != 0) return -1;
+    PSALM_CHECK_ARG(embeds && key_mask && cos_table && sin_table && refs && (uintptr_t)refs % 16 == 0 && hidden_out && workspace && N > 0 && S > 0 &&
+                        P_max > 0,
+                    "psalm_phi_suffix_grouped: null argument / table not 16-byte aligned / P_max < 1");
+    return phi_session_pass(d, true, embeds, key_mask, cos_table, sin_table, N, S, P_max, nullptr, 0, hidden_out, workspace, workspace_bytes,
+                            gemm_workspace, gemm_workspace_bytes, stream, refs);
 }
 
 // ================================================================================================= Swin tower

@@ -16,6 +16,7 @@ import sys
 from ctypes import c_char_p, c_float, c_int, c_long, c_void_p
 from typing import Optional, Sequence
 
+import numpy as np
 import torch
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
@@ -48,7 +49,7 @@ def _dt(t: torch.Tensor) -> int:
         raise PsalmHipError(f"unsupported dtype {t.dtype} (float32 / bfloat16 only)")
 
 
-ABI_VERSION = 9        # == PSALM_ABI_VERSION of include/psalm_hip.h (tests/test_0_abi.py compares the two and the built library's answer)
+ABI_VERSION = 10       # == PSALM_ABI_VERSION of include/psalm_hip.h (tests/test_0_abi.py compares the two and the built library's answer)
 
 
 class _ProfiledLib:
@@ -842,6 +843,27 @@ class Ops:
         self._check(rc, "psalm_phi_suffix")
         return out
 
+    def phi_suffix_grouped(self, desc, embeds, key_mask, cos, sin, N, S, refs, P_max, table=None):
+        """psalm_phi_suffix_grouped: phi_suffix for prompts of several sessions -- `refs`: the (num_layers, N) table of prefix_ref_table, as a host
+        array (uploaded here) or already on the device as bytes (then `table`, its host copy, is what gets checked)."""
+        if embeds.dtype != torch.float32 or embeds.dim() != 2 or embeds.shape[0] != N * S or embeds.shape[1] != desc.hidden or key_mask.numel() != N * S \
+                or cos.shape[0] < P_max + S:
+            raise PsalmHipError("phi_suffix_grouped: float32 (N*S, hidden) embeddings, key mask (N, S), tables of >= P_max + S rows")
+        refs = self._prefix_refs(refs, table, desc.num_layers * N, P_max, desc.heads, "phi_suffix_grouped")
+        self.lib.psalm_phi_suffix_grouped_workspace.restype = c_long
+        nbytes = self.lib.psalm_phi_suffix_grouped_workspace(ctypes.byref(desc), N, S)
+        if nbytes < 0:
+            raise PsalmHipError(f"psalm_phi_suffix_grouped_workspace: {self.lib.psalm_last_error().decode()}")
+        ws = self._stage_ws("phi_suffix", nbytes + 256)
+        off = (-ws.data_ptr()) % 256
+        out = self.empty(N * S, desc.hidden, dtype=torch.float32)
+        rc = self.lib.psalm_phi_suffix_grouped(ctypes.byref(desc), self._p(embeds), self._p(key_mask), self._p(cos), self._p(sin), N, S,
+                                               self._p(refs) if refs is not None else None, P_max, self._p(out),
+                                               c_void_p(ws.data_ptr() + off), c_long(nbytes), self._p(self._gemm_ws()),
+                                               c_long(self.GEMM_WS_BYTES), self._stream())
+        self._check(rc, "psalm_phi_suffix_grouped")
+        return out
+
     def x3_products(self, n: int):
         """f16 products formed per algorithmic product by this thread's split-f16 GEMMs: 3 (default, fp32-class) or 1 (hi.hi only: plain f16
         operands, a third of the matrix work -- the reduced-precision LLM side mode, not at the parity bar).  See psalm_gemm_x3_set_products."""
@@ -1171,6 +1193,79 @@ class Ops:
                                                               self._p(split_inv), self._p(cos), self._p(sin), self._p(key_mask), self._p(ws),
                                                               N, S, P, heads, head_dim, rot, self._stream())
         self._check(rc, "psalm_causal_attention_f32_prefix_split")
+        return split_out
+
+    # ---- grouped prefix form (PSALM.segment_many): every prompt names its own prefix cache, see psalm_causal_attention_f32_prefix_grouped
+    PREFIX_REF = np.dtype([("k_cache", "<u8"), ("v_cache", "<u8"), ("ldv", "<i8"), ("P", "<i4"), ("pad", "<i4")])        # psalm_prefix_ref
+
+    def prefix_ref_table(self, caches, prompt_cache, layers=None):
+        """The psalm_prefix_ref table of one grouped call as a HOST array of PREFIX_REF records, shape (len(layers), N): `caches` are (buf, views)
+        pairs of phi_prefix_cache (one per session), `prompt_cache[n]` the index into `caches` of prompt n, `layers` the layer indices (default:
+        all).  The caller puts it into its packed blob (or hands it to the grouped calls, which upload it) and keeps the caches alive."""
+        if not len(caches) or not len(prompt_cache):
+            raise PsalmHipError("prefix_ref_table: at least one cache and one prompt")
+        layers = range(len(caches[0][1])) if layers is None else layers
+        per = np.zeros((len(layers), len(caches)), self.PREFIX_REF)
+        for c, (_, views) in enumerate(caches):
+            for j, i in enumerate(layers):
+                kc, vc = views[i]
+                if kc.dtype != torch.float32 or vc.dtype != torch.float32 or not kc.is_contiguous() or vc.dim() != 2 or vc.stride(1) != 1 \
+                        or kc.dim() != 3 or kc.shape[1] != (vc.shape[0] + 31) // 32 * 32 or kc.shape[2] != 64 or vc.shape[1] < kc.shape[0] * 64:
+                    raise PsalmHipError("prefix cache: K (heads, ceil32(P), 64) float32 contiguous, V (P, >= heads*64) float32 rows")
+                per[j, c] = (kc.data_ptr(), vc.data_ptr(), vc.stride(0), vc.shape[0], 0)
+        idx = np.asarray(prompt_cache, np.int64)
+        if idx.min() < 0 or idx.max() >= len(caches):
+            raise PsalmHipError("prefix_ref_table: prompt_cache indexes `caches`")
+        return np.ascontiguousarray(per[:, idx])
+
+    def _prefix_refs(self, refs, table, n, P_max, heads, name):
+        """the device bytes of a table (uploading a host one); whatever host copy is at hand is checked against n entries, P_max and the entry rules"""
+        if isinstance(refs, np.ndarray):
+            table = refs
+            t = np.ascontiguousarray(refs)
+            refs = torch.from_numpy(t.view(np.uint8).reshape(-1).copy()).to(self.device)
+        if table is not None:
+            t = np.asarray(table)
+            if t.dtype != self.PREFIX_REF or t.size != n:
+                raise PsalmHipError(f"{name}: a table of {n} PREFIX_REF entries")
+            if (t["P"] < 1).any() or int(t["P"].max()) > P_max:
+                raise PsalmHipError(f"{name}: every table entry needs 1 <= P <= P_max = {P_max}")
+            if (t["k_cache"] == 0).any() or (t["v_cache"] == 0).any() or (t["k_cache"] % 16).any() or (t["v_cache"] % 16).any() \
+                    or (t["ldv"] < heads * 64).any() or (t["ldv"] % 4).any() or ((t["P"].astype(np.int64) - 1) * t["ldv"] * 4 + 256 >= 0x7fffffff).any():
+                raise PsalmHipError(f"{name}: table entries need 16-byte aligned caches, V rows of ldv >= heads * 64 floats, P * ldv * 4 below 2 GiB")
+        if refs is not None and (refs.dtype != torch.uint8 or refs.numel() != 32 * n or not refs.is_contiguous() or refs.data_ptr() % 16):
+            raise PsalmHipError(f"{name}: the device table is {n} x 32 contiguous bytes, 16-byte aligned")
+        return refs
+
+    def causal_attention_prefix_grouped(self, buf, q_off, k_off, v_off, refs, out, o_off, cos, sin, key_mask, N, S, P_max, heads, head_dim, rot,
+                                        table=None):
+        """causal_attention_prefix with one prefix per prompt: `refs` is the (N) table of prefix_ref_table (one layer), as a host array (uploaded here)
+        or as device bytes (then `table` may carry its host copy for the checks); cos / sin (>= P_max + S, rot)."""
+        if buf.dtype != torch.float32 or out.dtype != torch.float32 or cos.shape[0] < P_max + S or key_mask.numel() != N * S:
+            raise PsalmHipError("causal_attention_prefix_grouped: float32 buffers, cos / sin tables of >= P_max + S rows, key_mask (N, S)")
+        refs = self._prefix_refs(refs, table, N, P_max, heads, "causal_attention_prefix_grouped")
+        ws = self._prefix_attn_ws(N, S, heads)
+        rc = self.lib.psalm_causal_attention_f32_prefix_grouped(self._pv(buf), c_long(buf.stride(0)), q_off, k_off, v_off,
+                                                                self._p(refs) if refs is not None else None, P_max, self._pv(out),
+                                                                c_long(out.stride(0)), o_off, self._p(cos), self._p(sin), self._p(key_mask),
+                                                                self._p(ws), N, S, heads, head_dim, rot, self._stream())
+        self._check(rc, "psalm_causal_attention_f32_prefix_grouped")
+        return out
+
+    def causal_attention_prefix_grouped_split(self, buf, q_off, k_off, v_off, refs, split_out, split_inv, split_col_off, cos, sin, key_mask,
+                                              N, S, P_max, heads, head_dim, rot, table=None):
+        """causal_attention_prefix_grouped whose output leaves as causal_attention_prefix_split's does"""
+        if (buf.dtype != torch.float32 or split_out.dtype != torch.float16 or split_inv.dtype != torch.float32 or cos.shape[0] < P_max + S
+                or key_mask.numel() != N * S):
+            raise PsalmHipError("causal_attention_prefix_grouped_split: float32 qkv buffer, float16 split buffer, float32 scales, tables of >= P_max + S rows")
+        refs = self._prefix_refs(refs, table, N, P_max, heads, "causal_attention_prefix_grouped_split")
+        ws = self._prefix_attn_ws(N, S, heads)
+        rc = self.lib.psalm_causal_attention_f32_prefix_grouped_split(self._pv(buf), c_long(buf.stride(0)), q_off, k_off, v_off,
+                                                                      self._p(refs) if refs is not None else None, P_max, self._p(split_out),
+                                                                      c_long(split_out.stride(0)), split_out.shape[1] // 2, split_col_off,
+                                                                      self._p(split_inv), self._p(cos), self._p(sin), self._p(key_mask),
+                                                                      self._p(ws), N, S, heads, head_dim, rot, self._stream())
+        self._check(rc, "psalm_causal_attention_f32_prefix_grouped_split")
         return split_out
 
     def mha_attention(self, q, k, v, B, Lq, Lk, heads, mask=None, row_all_masked=None):

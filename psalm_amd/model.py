@@ -1507,23 +1507,31 @@ class PSALM:
                                           w["llm.final.g"], w["llm.final.b"])
         return self._cache[key]
 
-    def _llm_session(self, embeds, key_mask, B, L, P, cache, suffix: bool):
+    def _llm_session(self, embeds, key_mask, B, L, P, cache, suffix: bool, refs=None):
         """PSALM.llm cut behind the prompt-independent prefix.  suffix = False: the P prefix rows (B = 1, L = P), every layer's RoPE'd K and its V go
         into `cache` (Ops.phi_prefix_cache), the last layer stops behind its [k|v|q|fc1] GEMM; returns None.  suffix = True: the B * L suffix rows
         at positions P .., attention through the prefix kernel against `cache`; returns the final-LayerNorm hidden states (B*L, hidden).
         One native call each (psalm_phi_prefix / psalm_phi_suffix) under the conditions of PSALM.llm's stage-level call, else this op-by-op
-        sequence -- same launches, same bits (tests/test_11_session_emu.py)."""
+        sequence -- same launches, same bits (tests/test_11_session_emu.py).
+        refs (suffix only; `segment_many`): (device bytes, host array) of the (num_layers, B) psalm_prefix_ref table -- prompt b attends the cache and
+        prefix length its entries name, P is the largest of them and `cache` is not read; attention through the grouped prefix kernel
+        (psalm_phi_suffix_grouped, or the grouped ops in the same op-by-op sequence).  Off by default: the ungrouped path is untouched."""
         o, w, cfg = self.ops, self.w, self.cfg
         Hd, I = cfg.hidden_size, cfg.intermediate_size
         if cfg.head_dim != 64 or cfg.rotary_dim != 32:
             raise NotImplementedError("image sessions: the prefix attention kernel is built for head_dim 64 / rotary dim 32 (Phi-1.5)")
         cos, sin = self._rope(P + L if suffix else P)
-        buf, views = cache
+        buf, views = cache if refs is None else (None, None)
+        if refs is not None:
+            assert suffix, "a prefix pass writes one cache"
+            rdev, rhost = refs
         nh, hd, rd = cfg.num_heads, cfg.head_dim, cfg.rotary_dim
         fuse_split = self.fuse_split and (Hd + I) % 64 == 0 and Hd % 8 == 0 and "llm0.bnd" in w
         if fuse_split and self.c_stages and self.x3 and getattr(o.lib, "records", None) is None and not (H._DEBUG_BOUNDS or o.debug_bounds) \
                 and key_mask.is_contiguous():
             desc = self._phi_session_desc()
+            if refs is not None:
+                return o.phi_suffix_grouped(desc, embeds, key_mask, cos, sin, B, L, rdev, P, table=rhost)
             if suffix:
                 return o.phi_suffix(desc, embeds, key_mask, cos, sin, B, L, P, buf)
             o.phi_prefix(desc, embeds, key_mask, cos, sin, P, buf)
@@ -1543,11 +1551,16 @@ class PSALM:
         for i in range(cfg.num_layers):
             last = i == cfg.num_layers - 1
             ng, nb = (w["llm.final.g"], w["llm.final.b"]) if last else (w[f"llm{i + 1}.ln.g"], w[f"llm{i + 1}.ln.b"])
-            kc, vc = views[i]
+            if refs is None:
+                kc, vc = views[i]
+            else:
+                ri, rh = rdev[32 * B * i:32 * B * (i + 1)], rhost[i]
             if fuse_split:
                 o.gemm_x3_split(h, w[f"llm{i}.w1"], w[f"llm{i}.b1"], H.ACT_GELU_NEW, a2, inv2, w[f"llm{i}.bnd"], split_col_off=Hd,
                                 split_col_start=3 * Hd, act_col_start=3 * Hd, out=big, global_rows=True, paired=self.paired.get(f"llm{i}", False))
-                if suffix:
+                if refs is not None:
+                    o.causal_attention_prefix_grouped_split(big, 2 * Hd, 0, Hd, ri, a2, inv2, 0, cos, sin, key_mask, B, L, P, nh, hd, rd, table=rh)
+                elif suffix:
                     o.causal_attention_prefix_split(big, 2 * Hd, 0, Hd, kc, vc, a2, inv2, 0, cos, sin, key_mask, B, L, P, nh, hd, rd)
                 else:
                     o.phi_prefix_kv_store(big, 0, Hd, cos, sin, kc, vc, P, nh, hd, rd)
@@ -1563,7 +1576,9 @@ class PSALM:
                 continue
             o.gemm(h, w[f"llm{i}.w1"], w[f"llm{i}.b1"], act=H.ACT_GELU_NEW, act_col_start=3 * Hd, out=big)
             # columns: [k | v | q | gelu_new(fc1)];  attention output overwrites q in place (q was copied out by the RoPE pre-pass)
-            if suffix:
+            if refs is not None:
+                o.causal_attention_prefix_grouped(big, 2 * Hd, 0, Hd, ri, big, 2 * Hd, cos, sin, key_mask, B, L, P, nh, hd, rd, table=rh)
+            elif suffix:
                 o.causal_attention_prefix(big, 2 * Hd, 0, Hd, kc, vc, big, 2 * Hd, cos, sin, key_mask, B, L, P, nh, hd, rd)
             else:
                 o.phi_prefix_kv_store(big, 0, Hd, cos, sin, kc, vc, P, nh, hd, rd)
@@ -1701,6 +1716,161 @@ class PSALM:
             res = self._postprocess(r, self._post_sizes(Hi, Wi, seg_info[b], cfg.size_divisibility))
             outs.append(self._finalize(res, seg_info[b]))
         return outs
+
+    @torch.no_grad()
+    def segment_many(self, requests, *, postprocess: bool = True, region_point_sampler: Callable = default_region_point_sampler,
+                     stages: Optional[dict] = None):
+        """Prompts on SEVERAL images in one Phi pass: `requests` is a list of (session, kwargs) pairs, kwargs what `segment(session, **kwargs)` takes
+        for the prompt side (input_ids, attention_mask, seg_info, class_name_ids, ..., is_thing_list).  Returns one list per request, each what
+        `segment(session, **kwargs)` returns.  Every request obeys segment's rules on its own (session of this model and weights version, its
+        prompts agree up to and including <image>); requests may differ in image size, n_img, leading text and so in prefix length.  A session may
+        appear in several requests -- they share its one prefix cache, so they must share their leading text too.
+        The prefix caches are built or reused per session as `segment` does it; then ONE suffix pass runs over the prompts of all requests (S = the
+        bucketed maximum of their suffix lengths) with the grouped prefix attention, the row-set means and projector GEMMs run once, and the
+        predictor and post-processing run per prompt from its own session.
+        Region task: `region_point_sampler` is called request by request in list order, inside a request prompt by prompt and region by region --
+        the order a loop of `segment` calls over `requests` draws in.
+        `stages`: filled with the suffix rows' `inputs_embeds` / `hidden_states` ((N, S, hidden), N = all prompts in request order), `prefix_lens`
+        (per prompt) and `lengths`."""
+        self._session_mode_check()
+        requests = list(requests)
+        if not requests:
+            raise ValueError("segment_many: an empty request list")
+        o, w, cfg = self.ops, self.w, self.cfg
+        plans, arrays = [], {}
+        any_regions = False
+        for r, (session, kw) in enumerate(requests):
+            if not isinstance(session, ImageSession) or session.model is not self:
+                raise ValueError(f"segment_many: request {r}: this session was made by another model (or replica)")
+            if session.version != self._weights_version:
+                raise ValueError(f"segment_many: request {r}: the model's weights were prepared again after this session was made; encode the image again")
+            kw = dict(kw)
+            if self.seg_task == "panoptic" and postprocess:
+                assert kw.get("is_thing_list") is not None, "is_thing_list need to be given"
+                self.is_thing_list = kw["is_thing_list"]
+            ids = kw["input_ids"]
+            if ids.dim() == 1:
+                ids = ids[None]
+            N = int(ids.shape[0])
+            seg_info = kw.get("seg_info")
+            if seg_info is None:
+                seg_info = [session.seg_info if session.seg_info is not None else {}] * N
+            if len(seg_info) != N:
+                raise ValueError(f"segment_many: request {r}: one seg_info entry per prompt")
+            n_regions = None
+            if bool((ids == REGION_TOKEN_INDEX).any()):
+                pts, n_regions = self.region_points([s_["instances"].region_masks.tensor for s_ in seg_info], region_point_sampler)
+                arrays[f"region_img{r}"] = np.zeros(sum(n_regions), np.int32)         # every region pools from its own session's image
+                arrays[f"region_pts{r}"] = np.ascontiguousarray(pts.numpy(), np.float32)
+                any_regions = True
+            try:
+                sp = self._session_plan(session, ids, kw.get("attention_mask"), kw.get("class_name_ids"), kw.get("cls_indices"),
+                                        kw.get("token_refer_id"), n_regions, kw.get("class_name_embedding_indices") is not None,
+                                        kw.get("refer_embedding_indices") is not None)
+            except ValueError as e:
+                raise ValueError(f"segment_many: request {r}: {e}") from None
+            plans.append((session, sp, N, seg_info, n_regions))
+        for name in ("cls", "refer", "region"):
+            if len({sp[name] is None for _, sp, _, _, _ in plans}) != 1:
+                raise ValueError(f"segment_many: some requests carry {name} rows and some do not; all requests are prompts of the model's one task")
+        # the prefix caches, per session as segment builds / reuses them (a session listed twice: once)
+        caches, cache_of, seen = [], [], {}
+        for r, (session, sp, N, _, _) in enumerate(plans):
+            if id(session) in seen:
+                c, first = seen[id(session)]
+                if plans[first][1]["key"] != sp["key"] or plans[first][1]["P"] != sp["P"]:
+                    raise ValueError(f"segment_many: requests {first} and {r} share a session but not their leading text (one prefix cache per session)")
+            else:
+                c = len(caches)
+                caches.append(self._session_prefix(session, sp))
+                seen[id(session)] = (c, r)
+            cache_of += [c] * N
+        Nt = len(cache_of)
+        S = max(sp["S"] for _, sp, _, _, _ in plans)
+        P_max = max(sp["P"] for _, sp, _, _, _ in plans)
+        rhost = o.prefix_ref_table(caches, cache_of)
+        # the suffix plans side by side: prompt g of the call = prompt b of its request; rows re-based from (b, s) of (N_r, S_r) to (g, s) of (Nt, S)
+        sid = np.full((Nt, S), -1, np.int32)
+        srow = np.zeros((Nt, S), np.int32)
+        kmask = np.zeros((Nt, S), np.uint8)
+        sets = {name: ([np.zeros(1, np.int32)], []) for name in ("seg", "cls", "refer", "region") if plans[0][1][name] is not None}
+        g0 = reg0 = 0
+        for session, sp, N, _, n_regions in plans:
+            Sr = sp["S"]
+            sid[g0:g0 + N, :Sr], kmask[g0:g0 + N, :Sr] = sp["sid"], sp["kmask"]
+            assert not (sp["sid"] == 1).any(), "image rows live in the prefix"
+            srow[g0:g0 + N, :Sr] = sp["srow"] + np.where(sp["sid"] == 3, reg0, 0).astype(np.int32)      # region rows: into the concatenated features
+            for name, (offs, rows) in sets.items():
+                off, rw = sp[name]
+                n = int(off[-1])
+                rw = rw[:n].astype(np.int64)                     # (behind off[-1]: _session_plan's bucket padding)
+                rows.append(((rw // Sr + g0) * S + rw % Sr).astype(np.int32))
+                offs.append((off[1:].astype(np.int64) + int(offs[-1][-1])).astype(np.int32))
+            g0 += N
+            reg0 += sum(n_regions) if n_regions else 0
+        q = max(int(self.len_bucket or 0), 1)
+        for name, (offs, rows) in sets.items():
+            rows = np.concatenate(rows) if rows else np.zeros(0, np.int32)
+            if name != "seg" and q > 1:                           # (as _session_plan buckets the row-set lengths)
+                n = (rows.shape[0] + q - 1) // q * q
+                rows = np.concatenate((rows, np.zeros(max(n, q) - rows.shape[0], np.int32)))
+            arrays[name + "_off"], arrays[name + "_rows"] = np.concatenate(offs), rows
+        arrays["sid"], arrays["srow"], arrays["kmask"] = sid.reshape(-1), srow.reshape(-1), kmask.reshape(-1)
+        arrays["refs"] = rhost.view(np.uint8).reshape(-1)
+        blob, layout = self._pack(arrays)
+        dv = self._views(torch.from_numpy(blob).to(self.device), layout)
+        region_feats = None
+        if any_regions:
+            feats = []
+            for r, (session, sp, N, _, n_regions) in enumerate(plans):
+                if n_regions is None:
+                    continue
+                side = int(math.sqrt(session.n_img))
+                feats.append(o.region_pool(session.image_tokens, dv[f"region_img{r}"], dv[f"region_pts{r}"].view(sum(n_regions), -1, 2), side, side,
+                                           session.n_img))
+            region_feats = feats[0] if len(feats) == 1 else torch.cat(feats)
+        embeds = o.gather_rows([w["embed"], None, w["seg_query"], region_feats], dv["sid"], dv["srow"], cfg.hidden_size, out_dtype=torch.float32)
+        hidden = self._llm_session(embeds, dv["kmask"].view(Nt, S), Nt, S, P_max, None, suffix=True, refs=(dv["refs"], rhost))
+        if stages is not None:
+            stages.update(prefix_lens=[sp["P"] for _, sp, N, _, _ in plans for _ in range(N)],
+                          lengths=[l_ for _, sp, _, _, _ in plans for l_ in sp["lens"]],
+                          inputs_embeds=embeds.view(Nt, S, -1), hidden_states=hidden.view(Nt, S, -1))
+        Q = cfg.md_queries
+        seg_q = o.gemm(o.segment_mean(hidden, dv["seg_off"], dv["seg_rows"], out_dtype=self.adt), w["seg_query_projector.w"],
+                       w["seg_query_projector.b"], out_dtype=torch.float32)
+        cls_emb = seg_emb = reg_emb = None
+        if "cls_off" in dv:
+            cls_emb = o.gemm(o.segment_mean(hidden, dv["cls_off"], dv["cls_rows"], out_dtype=self.adt), w["class_name_projector.w"],
+                             w["class_name_projector.b"], out_dtype=self.wdt)
+        if "refer_off" in dv:
+            seg_emb = o.gemm(o.segment_mean(hidden, dv["refer_off"], dv["refer_rows"], out_dtype=self.adt), w["SEG_token_projector.w"],
+                             w["SEG_token_projector.b"], out_dtype=self.wdt)
+        if "region_off" in dv:
+            reg_emb = o.gemm(o.segment_mean(hidden, dv["region_off"], dv["region_rows"], out_dtype=self.adt), w["region_projector.w"],
+                             w["region_projector.b"], out_dtype=self.adt)
+        results = []
+        g = c0 = r0 = 0
+        for session, sp, N, seg_info, n_regions in plans:
+            mf, ms, shapes, mfs = session.mask_features, session.multi_scale_features, session.shapes, session.mask_features_size
+            Hi, Wi = int(session.images.shape[2]), int(session.images.shape[3])
+            outs = []
+            for b in range(N):
+                nc = sp["n_cls"][b]
+                ce = cls_emb[c0:c0 + nc] if cls_emb is not None else None
+                c0 += nc
+                se = seg_emb[g:g + 1] if seg_emb is not None else None
+                re = None
+                if reg_emb is not None:
+                    re = reg_emb[r0:r0 + n_regions[b]]
+                    r0 += n_regions[b]
+                res = self.predictor(ms, shapes, mf, mfs, seg_q[g * Q:(g + 1) * Q], se, ce, re,
+                                     kv=self._session_kv(session, n_regions[b] if n_regions else 0))
+                g += 1
+                if postprocess:
+                    res = self._finalize(self._postprocess(res, self._post_sizes(Hi, Wi, seg_info[b], cfg.size_divisibility)), seg_info[b])
+                outs.append(res)
+            results.append(outs)
+        return results
 
     # ======================================================================================= post-processing + eval_seg
     def _semantic(self, mflat, probsT, Kpad, want_mask_score=False):
