@@ -53,12 +53,16 @@ const char* psalm_backend(void); /* "hip-gfx950" */
  *                               psalm_swin_window_merge_ln_split) put 4 / 2 rows of <= 128 / 256 columns on one wavefront, psalm_patch_merge_ln keeps
  *                               an fp32 row of 512 / 1024 / 2048 values in registers, psalm_im2col_split_f16 gives few long rows a block each;
  *                               0: the r01-r05 forms (one row per wavefront)
- *   5..7                        unused */
+ *   PSALM_TUNE_MHA_QTILE_WAVES  1 (default): psalm_mha_attention_f32 gives every 16-query tile of a head a wavefront of its own (blocks of
+ *                               cdiv(Lq, 16) wavefronts that stage K / V together, double buffered); 0: the r05 kernel, one wavefront that
+ *                               walks all query tiles of the head
+ *   6..7                        unused */
 #define PSALM_TUNE_GEMM_XCD_KSPLIT 0
 #define PSALM_TUNE_ATTN_XCD_HEADS 1
 #define PSALM_TUNE_GEMM_MID 2
 #define PSALM_TUNE_DECODER_FUSE 3
 #define PSALM_TUNE_ROW_GROUPS 4
+#define PSALM_TUNE_MHA_QTILE_WAVES 5
 #define PSALM_TUNE_COUNT 8
 int psalm_set_tuning(int key, int value);
 int psalm_get_tuning(int key);

@@ -1465,30 +1465,33 @@ static int mha_f32_chunk(int B, int heads, int Lk) {
     c = (c + 63) / 64 * 64;
     return (int)(c < 64 ? 64 : (c > 256 ? 256 : c));
 }
+// The work of one wavefront on NQT query tiles (16 queries each, tiles t0 .. t0 + NQT - 1 of a head) -- the Q fragments, the mask rows and the
+// online-softmax state, the products against one staged 64-key K / V tile, the final store.  Both kernel forms below inline THIS code (the
+// one-wave kernel with all tiles of the head, the query-tile-parallel kernel with NQT = 1 and t0 = its wavefront): a tile's values are touched
+// only by its own instructions, in key order, so the two forms return the same words.
 template <int NQT>
-__global__ void __launch_bounds__(64) mha_attention_f32_mfma_kernel(const float* __restrict__ Q, long ldq, const float* __restrict__ K, long ldk,
-                                                                    const float* __restrict__ V, long ldv, float* __restrict__ O, long ldo,
-                                                                    const unsigned char* __restrict__ mask,
-                                                                    const unsigned char* __restrict__ row_all_masked, float* __restrict__ part,
-                                                                    int Lq, int Lk, int heads, int splits, int chunk, float scale) {
+struct MhaF32Tiles {
     typedef float f32x4 __attribute__((ext_vector_type(4)));
-    constexpr int HD = 32, LS = HD + 4, KT = 64;
-    __shared__ __attribute__((aligned(16))) float Ks[KT * LS];
-    __shared__ __attribute__((aligned(16))) float Vs[KT * LS];
-    const int lane = threadIdx.x, n16 = lane & 15, kk = lane >> 4;
-    const int sp = blockIdx.x, h = blockIdx.y, b = blockIdx.z;
-    const int k_lo = sp * chunk, k_hi = min(Lk, k_lo + chunk);
+    static constexpr int HD = 32, LS = HD + 4, KT = 64;
     float qf[NQT][8];
     const unsigned char* mrow[NQT];
     bool qok[NQT], use_m[NQT];
-    {
+    f32x4 o0[NQT], o1[NQT];
+    float m[NQT], l[NQT];
+    unsigned mbn[NQT];                                                    // blocked flags of the NEXT key tile (byte r = key kj + r)
+    int t0, n16, kk;
+    bool fast_mask;
+
+    __device__ __forceinline__ void init(const float* __restrict__ Q, long ldq, const unsigned char* __restrict__ mask,
+                                         const unsigned char* __restrict__ row_all_masked, int b, int h, int Lq, int Lk, float scale, int t0_, int lane) {
+        t0 = t0_; n16 = lane & 15; kk = lane >> 4;
         // r05: the query fragments and the rows' all-masked flags of ALL tiles are fetched before the first one is used (the flag load sat
         // behind a branch per tile: NQT dependent round trips before the first key tile; the flag address is always loadable)
         f32x4 qa[NQT], qc[NQT];
         unsigned char am[NQT];
 #pragma unroll
         for (int t = 0; t < NQT; ++t) {
-            const int qi = 16 * t + n16;
+            const int qi = 16 * (t0 + t) + n16;
             const float* p = Q + ((long)b * Lq + min(qi, Lq - 1)) * ldq + h * HD + 8 * kk;
             qa[t] = reinterpret_cast<const f32x4*>(p)[0];
             qc[t] = reinterpret_cast<const f32x4*>(p)[1];
@@ -1496,42 +1499,20 @@ __global__ void __launch_bounds__(64) mha_attention_f32_mfma_kernel(const float*
         }
 #pragma unroll
         for (int t = 0; t < NQT; ++t) {
-            const int qi = 16 * t + n16;
+            const int qi = 16 * (t0 + t) + n16;
             qok[t] = qi < Lq;
             qf[t][0] = qa[t].x * scale; qf[t][1] = qa[t].y * scale; qf[t][2] = qa[t].z * scale; qf[t][3] = qa[t].w * scale;
             qf[t][4] = qc[t].x * scale; qf[t][5] = qc[t].y * scale; qf[t][6] = qc[t].z * scale; qf[t][7] = qc[t].w * scale;
             // mask row of this lane's query (always a loadable address when a mask is given; `use_m` says whether it applies)
             mrow[t] = mask ? mask + ((long)b * Lq + min(qi, Lq - 1)) * Lk : nullptr;
             use_m[t] = mask && qok[t] && !am[t];
+            o0[t] = f32x4{0.f, 0.f, 0.f, 0.f}; o1[t] = f32x4{0.f, 0.f, 0.f, 0.f}; m[t] = -3.0e38f; l[t] = 0.f;
         }
+        fast_mask = mask && (Lk & 3) == 0 && (((uintptr_t)mask) & 3) == 0;
     }
-    const bool fast_mask = mask && (Lk & 3) == 0 && (((uintptr_t)mask) & 3) == 0;
-    f32x4 o0[NQT], o1[NQT];
-    float m[NQT], l[NQT];
-#pragma unroll
-    for (int t = 0; t < NQT; ++t) { o0[t] = f32x4{0.f, 0.f, 0.f, 0.f}; o1[t] = f32x4{0.f, 0.f, 0.f, 0.f}; m[t] = -3.0e38f; l[t] = 0.f; }
-    for (int kb = k_lo; kb < k_hi; kb += KT) {
-        __syncthreads();
-        {                                                                 // 64 keys x 8 float4 per operand (rows past Lk: clamped, masked below)
-            // r05: the 16 loads of a tile are all in flight before the first LDS store waits for one (rolled: 8 dependent round trips per tile)
-            f32x4 kt_[KT * (HD / 4) / 64], vt_[KT * (HD / 4) / 64];
-#pragma unroll
-            for (int i = 0; i < KT * (HD / 4) / 64; ++i) {
-                const int e = lane + 64 * i, r = e >> 3, c4 = (e & 7) * 4;
-                const long row = (long)b * Lk + min(kb + r, Lk - 1);
-                kt_[i] = *reinterpret_cast<const f32x4*>(K + row * ldk + h * HD + c4);
-                vt_[i] = *reinterpret_cast<const f32x4*>(V + row * ldv + h * HD + c4);
-            }
-            PSALM_SCHED_FENCE();
-#pragma unroll
-            for (int i = 0; i < KT * (HD / 4) / 64; ++i) {
-                const int e = lane + 64 * i, r = e >> 3, c4 = (e & 7) * 4;
-                *reinterpret_cast<f32x4*>(&Ks[r * LS + c4]) = kt_[i];
-                *reinterpret_cast<f32x4*>(&Vs[r * LS + c4]) = vt_[i];
-            }
-        }
-        __syncthreads();
-        unsigned mbn[NQT];                                                // blocked flags of the NEXT key tile (byte r = key kj + r)
+
+    // the keys kb .. min(kb + 64, k_hi) - 1, staged in Ks / Vs (64 rows of LS floats)
+    __device__ __forceinline__ void key_tile(const float* Ks, const float* Vs, const unsigned char* __restrict__ mask, int kb, int k_hi, int Lk) {
 #pragma unroll
         for (int t = 0; t < NQT; ++t) mbn[t] = fast_mask ? *reinterpret_cast<const unsigned*>(mrow[t] + min(kb + 4 * kk, Lk - 4)) : 0u;
 #pragma unroll 1
@@ -1613,22 +1594,124 @@ __global__ void __launch_bounds__(64) mha_attention_f32_mfma_kernel(const float*
             }
         }
     }
+
+    // direct normalised output when the keys are not split, else the partial state [O (32) | m | l | pad 2] per (b, h, split, q)
+    __device__ __forceinline__ void store(float* __restrict__ O, long ldo, float* __restrict__ part, int b, int h, int sp, int Lq, int heads, int splits) const {
 #pragma unroll
-    for (int t = 0; t < NQT; ++t) {
-        const int qi = 16 * t + n16;
-        if (!qok[t]) continue;
-        if (splits == 1) {
-            const float inv = l[t] > 0.f ? 1.f / l[t] : 0.f;
-            float* op = O + ((long)b * Lq + qi) * ldo + h * HD + 4 * kk;
-            *reinterpret_cast<psalm_f32x4*>(op) = psalm_f32x4{o0[t][0] * inv, o0[t][1] * inv, o0[t][2] * inv, o0[t][3] * inv};
-            *reinterpret_cast<psalm_f32x4*>(op + 16) = psalm_f32x4{o1[t][0] * inv, o1[t][1] * inv, o1[t][2] * inv, o1[t][3] * inv};
-        } else {                                                          // partial state: [O (32) | m | l | pad 2] per (b, h, split, q)
-            float* pp = part + ((((long)b * heads + h) * splits + sp) * Lq + qi) * 36;
-            *reinterpret_cast<psalm_f32x4*>(pp + 4 * kk) = psalm_f32x4{o0[t][0], o0[t][1], o0[t][2], o0[t][3]};
-            *reinterpret_cast<psalm_f32x4*>(pp + 16 + 4 * kk) = psalm_f32x4{o1[t][0], o1[t][1], o1[t][2], o1[t][3]};
-            if (kk == 0) { pp[32] = m[t]; pp[33] = l[t]; }
+        for (int t = 0; t < NQT; ++t) {
+            const int qi = 16 * (t0 + t) + n16;
+            if (!qok[t]) continue;
+            if (splits == 1) {
+                const float inv = l[t] > 0.f ? 1.f / l[t] : 0.f;
+                float* op = O + ((long)b * Lq + qi) * ldo + h * HD + 4 * kk;
+                *reinterpret_cast<psalm_f32x4*>(op) = psalm_f32x4{o0[t][0] * inv, o0[t][1] * inv, o0[t][2] * inv, o0[t][3] * inv};
+                *reinterpret_cast<psalm_f32x4*>(op + 16) = psalm_f32x4{o1[t][0] * inv, o1[t][1] * inv, o1[t][2] * inv, o1[t][3] * inv};
+            } else {
+                float* pp = part + ((((long)b * heads + h) * splits + sp) * Lq + qi) * 36;
+                *reinterpret_cast<psalm_f32x4*>(pp + 4 * kk) = psalm_f32x4{o0[t][0], o0[t][1], o0[t][2], o0[t][3]};
+                *reinterpret_cast<psalm_f32x4*>(pp + 16 + 4 * kk) = psalm_f32x4{o1[t][0], o1[t][1], o1[t][2], o1[t][3]};
+                if (kk == 0) { pp[32] = m[t]; pp[33] = l[t]; }
+            }
         }
     }
+};
+
+template <int NQT>
+__global__ void __launch_bounds__(64) mha_attention_f32_mfma_kernel(const float* __restrict__ Q, long ldq, const float* __restrict__ K, long ldk,
+                                                                    const float* __restrict__ V, long ldv, float* __restrict__ O, long ldo,
+                                                                    const unsigned char* __restrict__ mask,
+                                                                    const unsigned char* __restrict__ row_all_masked, float* __restrict__ part,
+                                                                    int Lq, int Lk, int heads, int splits, int chunk, float scale) {
+    typedef float f32x4 __attribute__((ext_vector_type(4)));
+    constexpr int HD = 32, LS = HD + 4, KT = 64;
+    __shared__ __attribute__((aligned(16))) float Ks[KT * LS];
+    __shared__ __attribute__((aligned(16))) float Vs[KT * LS];
+    const int lane = threadIdx.x;
+    const int sp = blockIdx.x, h = blockIdx.y, b = blockIdx.z;
+    const int k_lo = sp * chunk, k_hi = min(Lk, k_lo + chunk);
+    MhaF32Tiles<NQT> st;
+    st.init(Q, ldq, mask, row_all_masked, b, h, Lq, Lk, scale, 0, lane);
+    for (int kb = k_lo; kb < k_hi; kb += KT) {
+        __syncthreads();
+        {                                                                 // 64 keys x 8 float4 per operand (rows past Lk: clamped, masked below)
+            // r05: the 16 loads of a tile are all in flight before the first LDS store waits for one (rolled: 8 dependent round trips per tile)
+            f32x4 kt_[KT * (HD / 4) / 64], vt_[KT * (HD / 4) / 64];
+#pragma unroll
+            for (int i = 0; i < KT * (HD / 4) / 64; ++i) {
+                const int e = lane + 64 * i, r = e >> 3, c4 = (e & 7) * 4;
+                const long row = (long)b * Lk + min(kb + r, Lk - 1);
+                kt_[i] = *reinterpret_cast<const f32x4*>(K + row * ldk + h * HD + c4);
+                vt_[i] = *reinterpret_cast<const f32x4*>(V + row * ldv + h * HD + c4);
+            }
+            PSALM_SCHED_FENCE();
+#pragma unroll
+            for (int i = 0; i < KT * (HD / 4) / 64; ++i) {
+                const int e = lane + 64 * i, r = e >> 3, c4 = (e & 7) * 4;
+                *reinterpret_cast<f32x4*>(&Ks[r * LS + c4]) = kt_[i];
+                *reinterpret_cast<f32x4*>(&Vs[r * LS + c4]) = vt_[i];
+            }
+        }
+        __syncthreads();
+        st.key_tile(Ks, Vs, mask, kb, k_hi, Lk);
+    }
+    st.store(O, ldo, part, b, h, sp, Lq, heads, splits);
+}
+
+// ... the query-tile-parallel form (PSALM_TUNE_MHA_QTILE_WAVES, the default).  The one-wave kernel runs the NQT tiles' dependent fp32 chains one
+// after the other in one wavefront (112 MFMAs + 7 x 60 VALU instructions per 16-key sub-tile at 148 registers: nothing to overlap with; the
+// 100 x 100 self-attention is 16 wavefronts on the whole chip).  Here the same grid (splits, heads, B), but a block is NW wavefronts and
+// wavefront w owns query tile w alone.  The block stages each 64-key K / V tile once, all 64 * NW threads together, into one of TWO LDS
+// buffers: tile i + 1's global loads are issued before tile i's products and stored after them -- one block barrier per tile.
+template <int NW>
+__global__ void __launch_bounds__(64 * NW) mha_attention_f32_qtile_kernel(const float* __restrict__ Q, long ldq, const float* __restrict__ K, long ldk,
+                                                                         const float* __restrict__ V, long ldv, float* __restrict__ O, long ldo,
+                                                                         const unsigned char* __restrict__ mask,
+                                                                         const unsigned char* __restrict__ row_all_masked, float* __restrict__ part,
+                                                                         int Lq, int Lk, int heads, int splits, int chunk, float scale) {
+    typedef float f32x4 __attribute__((ext_vector_type(4)));
+    constexpr int HD = 32, LS = HD + 4, KT = 64, NT = 64 * NW, NE = KT * (HD / 4), NL = (NE + NT - 1) / NT;   // NE float4 per operand tile, NL per thread
+    __shared__ __attribute__((aligned(16))) float Ks[2][KT * LS];
+    __shared__ __attribute__((aligned(16))) float Vs[2][KT * LS];
+    const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
+    const int sp = blockIdx.x, h = blockIdx.y, b = blockIdx.z;
+    const int k_lo = sp * chunk, k_hi = min(Lk, k_lo + chunk);
+    f32x4 kt_[NL], vt_[NL];
+    auto fetch = [&](int kb) {                                            // rows past Lk: clamped, masked in the products
+#pragma unroll
+        for (int i = 0; i < NL; ++i) {
+            const int e = tid + NT * i, r = e >> 3, c4 = (e & 7) * 4;
+            if (NE % NT == 0 || e < NE) {
+                const long row = (long)b * Lk + min(kb + r, Lk - 1);
+                kt_[i] = *reinterpret_cast<const f32x4*>(K + row * ldk + h * HD + c4);
+                vt_[i] = *reinterpret_cast<const f32x4*>(V + row * ldv + h * HD + c4);
+            }
+        }
+    };
+    auto park = [&](int buf) {
+#pragma unroll
+        for (int i = 0; i < NL; ++i) {
+            const int e = tid + NT * i, r = e >> 3, c4 = (e & 7) * 4;
+            if (NE % NT == 0 || e < NE) {
+                *reinterpret_cast<f32x4*>(&Ks[buf][r * LS + c4]) = kt_[i];
+                *reinterpret_cast<f32x4*>(&Vs[buf][r * LS + c4]) = vt_[i];
+            }
+        }
+    };
+    fetch(k_lo);                                                          // (in flight while the query fragments are fetched)
+    MhaF32Tiles<1> st;
+    st.init(Q, ldq, mask, row_all_masked, b, h, Lq, Lk, scale, w, lane);
+    PSALM_SCHED_FENCE();
+    park(0);
+    int buf = 0;
+    for (int kb = k_lo; kb < k_hi; kb += KT, buf ^= 1) {
+        // this tile's stores are visible; every wavefront is done with the other buffer (its products of the tile before)
+        __syncthreads();
+        const bool more = kb + KT < k_hi;
+        if (more) fetch(kb + KT);
+        st.key_tile(Ks[buf], Vs[buf], mask, kb, k_hi, Lk);
+        if (more) park(buf ^ 1);
+    }
+    st.store(O, ldo, part, b, h, sp, Lq, heads, splits);
 }
 
 // merge of the key chunks: thread = (b, h, q, d); weights e^(m_s - M)
@@ -1709,8 +1792,14 @@ extern "C" int psalm_mha_attention_f32(const float* q, long ldq, const float* k,
     const dim3 grid(splits, heads, B);
     const int nqt = cdiv(Lq, 16);
     hipStream_t s = (hipStream_t)stream;
-#define MHA_F32_LAUNCH(N_) hipLaunchKernelGGL((mha_attention_f32_mfma_kernel<N_>), grid, dim3(64), 0, s, q, ldq, k, ldk, v, ldv, out, ldo, mask, \
-                                              row_all_masked, (float*)workspace, Lq, Lk, heads, splits, chunk, scale)
+#define MHA_F32_LAUNCH(N_)                                                                                                                          \
+    do {                                                                                                                                            \
+        if (qtile) hipLaunchKernelGGL((mha_attention_f32_qtile_kernel<N_>), grid, dim3(64 * N_), 0, s, q, ldq, k, ldk, v, ldv, out, ldo, mask,      \
+                                      row_all_masked, (float*)workspace, Lq, Lk, heads, splits, chunk, scale);                                      \
+        else hipLaunchKernelGGL((mha_attention_f32_mfma_kernel<N_>), grid, dim3(64), 0, s, q, ldq, k, ldk, v, ldv, out, ldo, mask, row_all_masked,  \
+                                (float*)workspace, Lq, Lk, heads, splits, chunk, scale);                                                            \
+    } while (0)
+    const bool qtile = psalm_get_tuning(PSALM_TUNE_MHA_QTILE_WAVES) != 0;       // a wavefront per query tile (default) / one wavefront for all tiles
     if (nqt <= 1) MHA_F32_LAUNCH(1);
     else if (nqt <= 2) MHA_F32_LAUNCH(2);
     else if (nqt <= 4) MHA_F32_LAUNCH(4);

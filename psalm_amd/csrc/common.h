@@ -202,6 +202,7 @@ extern "C" int psalm_get_tuning(int key);          // api.hip; keys: PSALM_TUNE_
 #define PSALM_TUNE_GEMM_MID 2
 #define PSALM_TUNE_DECODER_FUSE 3
 #define PSALM_TUNE_ROW_GROUPS 4
+#define PSALM_TUNE_MHA_QTILE_WAVES 5
 #define PSALM_TUNE_COUNT 8
 #endif
 

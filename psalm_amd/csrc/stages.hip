@@ -575,19 +575,19 @@ extern "C" int psalm_pixel_decoder_forward(const psalm_pd_desc* d, const float* 
         PD(psalm_gemm_x3_split(sp1, 2L * KpD, inv1, ly->l1_w, 2L * KpD, ly->l1_ws, KpD, ly->l1_b, nullptr, 0, S, F, /*relu*/ 1, 0, hdd, 2L * Kf, Kf, 0, 0, ly->l1_paired, hddinv,
                                ly->l1_bnd, 0, gemm_workspace, gemm_workspace_bytes, stream));
         PD(psalm_gemm_x3(hdd, 2L * Kf, hddinv, ly->l2_w, 2L * Kf, ly->l2_ws, Kf, ly->l2_b, sn, D, x1, D, S, D, 0, 0, gemm_workspace, gemm_workspace_bytes, stream));
-        // norm2: fp32 stream (-> sc: the layer's input buffer is free again) + the NEXT layer's operands: split(src) and split(src + pos)
-        PD(psalm_layernorm_split(x1, D, sc, D, ly->n2_g, ly->n2_b, S, D, eps, more ? sp2 : nullptr, more ? inv2 : nullptr, more ? lvl_pos : nullptr, more ? S : 0,
-                                 more ? sp3 : nullptr, more ? inv3 : nullptr, stream));
+        // norm2: fp32 stream (-> sc: the layer's input buffer is free again; the last layer's goes straight to `ms_out`) + the NEXT layer's
+        // operands: split(src) and split(src + pos)
+        PD(psalm_layernorm_split(x1, D, more ? sc : ms_out, D, ly->n2_g, ly->n2_b, S, D, eps, more ? sp2 : nullptr, more ? inv2 : nullptr, more ? lvl_pos : nullptr,
+                                 more ? S : 0, more ? sp3 : nullptr, more ? inv3 : nullptr, stream));
         // (the stream stays in src[cur])
     }
-    PD(psalm_copy_d2d(ms_out, src[cur], (long)S * D * 4, stream));
     // ---- FPN step on res2 + mask features
     {
         const int C2 = d->in_dims[0], Kp2 = c64(C2), hs = g.h[1], ws_ = g.w[1], H2 = g.h[0], W2 = g.w[0], K9 = 9 * D, Kp9 = c64(K9);
         PD(psalm_split_f16(feats_host[0], C2, tokp, 2L * Kp2, tokinv, HW2, C2, stream));
         PD(psalm_gemm_x3(tokp, 2L * Kp2, tokinv, d->adapter_w, 2L * Kp2, d->adapter_ws, Kp2, d->adapter_b, nullptr, 0, lat, D, HW2, D, 0, 0, gemm_workspace, gemm_workspace_bytes, stream));
         PD(psalm_groupnorm_nhwc(lat, PSALM_F32, lat2, PSALM_F32, d->adapter_gn_g, d->adapter_gn_b, gnws, 1, HW2, D, d->G, eps, 1, stream));
-        PD(psalm_upsample_add_nhwc(lat2, PSALM_F32, src[cur] + g.start[2] * D, PSALM_F32, y, PSALM_F32, 1, hs, ws_, H2, W2, D, stream));
+        PD(psalm_upsample_add_nhwc(lat2, PSALM_F32, ms_out + g.start[2] * D, PSALM_F32, y, PSALM_F32, 1, hs, ws_, H2, W2, D, stream));
         PD(psalm_im2col_split_f16(y, cols, colsinv, 1, H2, W2, D, 3, 1, 1, stream));
         PD(psalm_gemm_x3(cols, 2L * Kp9, colsinv, d->layer_w, 2L * Kp9, d->layer_ws, Kp9, d->layer_b, nullptr, 0, y2, D, HW2, D, 0, 0, gemm_workspace, gemm_workspace_bytes, stream));
         PD(psalm_groupnorm_nhwc(y2, PSALM_F32, y, PSALM_F32, d->layer_gn_g, d->layer_gn_b, gnws, 1, HW2, D, d->G, eps, 1, stream));
@@ -731,27 +731,33 @@ extern "C" int psalm_predictor_forward(const psalm_pr_desc* d, const float* cons
     const bool mf_split = HW2 > 4096;
     // (fused LayerNorm chain / paired projections: D % 8 == 0, the skinny GEMM's M <= 192; PSALM_TUNE_DECODER_FUSE switches them off)
     const bool fuse = D % 8 == 0 && D <= 2048 && Q <= 192 && psalm_get_tuning(PSALM_TUNE_DECODER_FUSE) != 0;
-    auto mask_head = [&](const float* out_, bool have_dec = false) -> int {   // decoder_norm -> mask_embed MLP -> (Q, H2*W2) mask logits; `dec` stays for the class heads
+    // decoder_norm -> mask_embed MLP -> (Q, H2*W2) mask logits into `dst`; `dec` stays for the class heads.  `next`: the decoder layer that follows -- its
+    // cross-attention query projection (outq -> qp; both operands exist by now and qp is free) shares the launch of the MLP's first layer
+    auto mask_head = [&](const float* out_, bool have_dec, const psalm_pr_layer* next, float* dst) -> int {
         int r;
         if (!have_dec && (r = ln(out_, d->dn_g, d->dn_b, dec, Q))) return r;
-        if ((r = g32(dec, Q, D, d->mask_embed_w[0], d->mask_embed_b[0], nullptr, me0, D, 1))) return r;
+        if (fuse && next) {
+            if ((r = psalm_gemm_f32_pair(dec, d->mask_embed_w[0], d->mask_embed_b[0], me0, Q, D, D, 1, outq, next->cq_w, next->cq_b, qp, Q, D, D, 0, stream))) return r;
+        } else if ((r = g32(dec, Q, D, d->mask_embed_w[0], d->mask_embed_b[0], nullptr, me0, D, 1))) return r;
         if ((r = g32(me0, Q, D, d->mask_embed_w[1], d->mask_embed_b[1], nullptr, me1, D, 1))) return r;
         if ((r = g32(me1, Q, D, d->mask_embed_w[2], d->mask_embed_b[2], nullptr, me2, MD, 0))) return r;
         if (mf_split) {
             if ((r = psalm_split_f16(me2, MD, mes, 2L * KpM, mesinv, Q, MD, stream))) return r;
-            return psalm_gemm_x3(mes, 2L * KpM, mesinv, mfp, 2L * KpM, mfinv, KpM, nullptr, nullptr, 0, masks, HW2, Q, HW2, 0, 0, gemm_workspace, gemm_workspace_bytes, stream);
+            return psalm_gemm_x3(mes, 2L * KpM, mesinv, mfp, 2L * KpM, mfinv, KpM, nullptr, nullptr, 0, dst, HW2, Q, HW2, 0, 0, gemm_workspace, gemm_workspace_bytes, stream);
         }
-        return g32(me2, Q, MD, mask_features, nullptr, nullptr, masks, HW2, 0);
+        return g32(me2, Q, MD, mask_features, nullptr, nullptr, dst, HW2, 0);
     };
     const float* out = seg_query;
-    PR(mask_head(out));
-    PR(psalm_add_bcast(out, PSALM_F32, d->query_embed, PSALM_F32, outq, PSALM_F32, Q, D, Q, stream));
+    // (fuse: `+ query_embed` first, layer 0's query projection rides with the mask head)
+    if (fuse) PR(psalm_add_bcast(out, PSALM_F32, d->query_embed, PSALM_F32, outq, PSALM_F32, Q, D, Q, stream));
+    PR(mask_head(out, false, &d->layers[0], masks));
+    if (!fuse) PR(psalm_add_bcast(out, PSALM_F32, d->query_embed, PSALM_F32, outq, PSALM_F32, Q, D, Q, stream));
     int cur = 0;
     for (int i = 0; i < nl; ++i) {
         const psalm_pr_layer* ly = &d->layers[i];
         const int l = i % nlev, j = i / nlev, h = hw_levels_host[2 * l], w = hw_levels_host[2 * l + 1], hw = h * w, N = nl_l[l] * D;
         PR(psalm_attn_mask(masks, amask, flags, Q, H2, W2, h, w, stream));
-        PR(g32(outq, Q, D, ly->cq_w, ly->cq_b, nullptr, qp, D, 0));
+        if (!fuse) PR(g32(outq, Q, D, ly->cq_w, ly->cq_b, nullptr, qp, D, 0));       // (fuse: issued with the mask head in front of this layer)
         PR(psalm_mha_attention_f32(qp, D, Kl[l] + (long)j * D, N, Vl[l] + (long)j * D, N, a, D, amask, flags, mha, 1, Q, hw, nh, 32, stream));
         PR(g32(a, Q, D, ly->co_w, ly->co_b, out, x1, D, 0));
         float* o1 = outb[cur];
@@ -779,28 +785,51 @@ extern "C" int psalm_predictor_forward(const psalm_pr_desc* d, const float* cons
             PR(psalm_add_bcast(o1, PSALM_F32, d->query_embed, PSALM_F32, outq, PSALM_F32, Q, D, Q, stream));
         }
         out = o1;
-        PR(mask_head(out, fuse));
+        // (the last layer's mask logits are the result: straight into `pred_masks`)
+        PR(mask_head(out, fuse, i + 1 < nl ? &d->layers[i + 1] : nullptr, i + 1 < nl ? masks : pred_masks));
         cur ^= 1;
     }
-    PR(psalm_copy_d2d(pred_masks, masks, (long)Q * HW2 * 4, stream));
     // ---- prediction heads of the LAST layer (the earlier ones are auxiliary training outputs, TD:672-690)
+    // Each head: dec -> relu(W0) -> W1 -> product with the prompt embeddings (region: einsum 'kd,ld->kl' (TD:744): (k, Q), the embeddings are the A
+    // operand).  The heads are independent of one another: with `fuse` the first two requested go through psalm_gemm_f32_pair layer by layer (the
+    // second one's intermediates in me0 / me1, free after the last mask head); a third, or an embedding product outside the pair kernel's range
+    // (M <= 192, N <= 8192), is issued on its own.
+    struct Head { const float* w0; const float* b0; const float* w1; const float* b1; const float* A; const float* W; float* C; int M, N; float* h0; float* h1; };
+    Head hd[3];
+    int nh_ = 0;
     if (class_emb && n_cls > 0) {
         PSALM_CHECK_ARG(cls_logits != nullptr, "psalm_predictor_forward: cls_logits output missing");
-        PR(g32(dec, Q, D, d->CLASS_w[0], d->CLASS_b[0], nullptr, t0, D, 1));
-        PR(g32(t0, Q, D, d->CLASS_w[1], d->CLASS_b[1], nullptr, t1, D, 0));
-        PR(g32(t1, Q, D, class_emb, nullptr, nullptr, cls_logits, n_cls, 0));
+        hd[nh_++] = Head{d->CLASS_w[0], d->CLASS_b[0], d->CLASS_w[1], d->CLASS_b[1], nullptr, class_emb, cls_logits, Q, n_cls, nullptr, nullptr};
     }
     if (seg_emb && n_seg > 0) {
         PSALM_CHECK_ARG(seg_logits != nullptr, "psalm_predictor_forward: seg_logits output missing");
-        PR(g32(dec, Q, D, d->SEG_w[0], d->SEG_b[0], nullptr, t0, D, 1));
-        PR(g32(t0, Q, D, d->SEG_w[1], d->SEG_b[1], nullptr, t1, D, 0));
-        PR(g32(t1, Q, D, seg_emb, nullptr, nullptr, seg_logits, n_seg, 0));
+        hd[nh_++] = Head{d->SEG_w[0], d->SEG_b[0], d->SEG_w[1], d->SEG_b[1], nullptr, seg_emb, seg_logits, Q, n_seg, nullptr, nullptr};
     }
-    if (region_emb && n_reg > 0) {                               // einsum 'kd,ld->kl' (TD:744): (k, Q)
+    if (region_emb && n_reg > 0) {
         PSALM_CHECK_ARG(region_logits != nullptr, "psalm_predictor_forward: region_logits output missing");
-        PR(g32(dec, Q, D, d->REGION_w[0], d->REGION_b[0], nullptr, t0, D, 1));
-        PR(g32(t0, Q, D, d->REGION_w[1], d->REGION_b[1], nullptr, t1, D, 0));
-        PR(g32(region_emb, n_reg, D, t1, nullptr, nullptr, region_logits, Q, 0));
+        hd[nh_++] = Head{d->REGION_w[0], d->REGION_b[0], d->REGION_w[1], d->REGION_b[1], region_emb, nullptr, region_logits, n_reg, Q, nullptr, nullptr};
+    }
+    auto emb = [&](const Head& x) -> int {                       // the head's last product (A or W is its own h1)
+        return g32(x.A ? x.A : x.h1, x.M, D, x.W ? x.W : x.h1, nullptr, nullptr, x.C, x.N, 0);
+    };
+    const bool pair = fuse && nh_ >= 2;
+    int first = 0;
+    if (pair) {
+        Head& x = hd[0]; Head& y = hd[1];
+        x.h0 = t0; x.h1 = t1; y.h0 = me0; y.h1 = me1;
+        PR(psalm_gemm_f32_pair(dec, x.w0, x.b0, x.h0, Q, D, D, 1, dec, y.w0, y.b0, y.h0, Q, D, D, 1, stream));
+        PR(psalm_gemm_f32_pair(x.h0, x.w1, x.b1, x.h1, Q, D, D, 0, y.h0, y.w1, y.b1, y.h1, Q, D, D, 0, stream));
+        if (x.M <= 192 && y.M <= 192 && x.N <= 8192 && y.N <= 8192)
+            PR(psalm_gemm_f32_pair(x.A ? x.A : x.h1, x.W ? x.W : x.h1, nullptr, x.C, x.M, x.N, D, 0, y.A ? y.A : y.h1, y.W ? y.W : y.h1, nullptr, y.C, y.M, y.N, D, 0, stream));
+        else { PR(emb(x)); PR(emb(y)); }
+        first = 2;
+    }
+    for (int i = first; i < nh_; ++i) {
+        Head& x = hd[i];
+        x.h0 = t0; x.h1 = t1;
+        PR(g32(dec, Q, D, x.w0, x.b0, nullptr, x.h0, D, 1));
+        PR(g32(x.h0, Q, D, x.w1, x.b1, nullptr, x.h1, D, 0));
+        PR(emb(x));
     }
 #undef PR
     return 0;
