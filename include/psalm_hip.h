@@ -35,8 +35,10 @@ const char* psalm_last_error(void);
  *    psalm_phi_suffix (+ their _workspace / _cache_bytes functions).
  * 9: video object tracking: psalm_video_pick, psalm_video_fuse (+ _workspace), psalm_mask_resize_nearest_pad, psalm_mask_select_points.
  * 10: grouped image sessions: psalm_prefix_ref, psalm_causal_attention_f32_prefix_grouped[_split] (+ _workspace), the stage-level
- *    psalm_phi_suffix_grouped (+ _workspace). */
-#define PSALM_ABI_VERSION 10
+ *    psalm_phi_suffix_grouped (+ _workspace).
+ * 11: the mask decoder over all prompts of an image session: psalm_mha_attention_f32_shared (+ _workspace), psalm_gemm_f32_rows[_pair],
+ *    psalm_gemm_f32_grouped, psalm_predictor_kv_bytes, the stage-level psalm_predictor_forward_batched (+ _workspace). */
+#define PSALM_ABI_VERSION 11
 int psalm_abi_version(void);
 const char* psalm_backend(void); /* "hip-gfx950" */
 
@@ -229,6 +231,13 @@ long psalm_mha_attention_f32_workspace(int B, int heads, int Lq, int Lk);
 int psalm_mha_attention_f32(const float* q, long ldq, const float* k, long ldk, const float* v, long ldv, float* out, long ldo,
                             const unsigned char* mask, const unsigned char* row_all_masked, void* workspace, int B, int Lq, int Lk, int heads,
                             int head_dim, void* stream);
+/* ... B query sets against ONE K / V (batch stride 0): q / out (B*Lq, ..), mask (B*Lq, Lk), row_all_masked (B*Lq) per set, k / v (Lk, ..) once.
+ * The key chunk is that of a B = 1 call of psalm_mha_attention_f32 whatever B is, so set b's output -- and its partial states, the b-th
+ * heads * splits * Lq * 36 floats of the workspace -- are, word for word, those of that call on set b alone. */
+long psalm_mha_attention_f32_shared_workspace(int B, int heads, int Lq, int Lk);
+int psalm_mha_attention_f32_shared(const float* q, long ldq, const float* k, long ldk, const float* v, long ldv, float* out, long ldo,
+                                   const unsigned char* mask, const unsigned char* row_all_masked, void* workspace, int B, int Lq, int Lk,
+                                   int heads, int head_dim, void* stream);
 
 /* Phi prefill attention (modeling_phi.py:189-245; eager softmax :137-160; partial RoPE :92-122) for fp32 buffers on the fp32 matrix cores,
  * split over keys inside a block (fp32 / f16x3 modes).  Operands as psalm_causal_attention + a 16-byte aligned workspace of
@@ -337,6 +346,18 @@ int psalm_layernorm_chain(const float* x, long ldx, float* y1, long ldy1, const 
  * psalm_gemm calls with float32 operands. */
 int psalm_gemm_f32_pair(const float* A0, const float* W0, const float* bias0, float* C0, int M0, int N0, int K0, int act0, const float* A1,
                         const float* W1, const float* bias1, float* C1, int M1, int N1, int K1, int act1, void* stream);
+/* The exact-fp32 skinny kernel of psalm_gemm (float32 operands, M <= 192) over many row tiles: every output element follows from its A row, its
+ * W row and K alone, so row r carries the words psalm_gemm returns for any <= 192-row set holding it.
+ *   psalm_gemm_f32_rows        C = act(A . W^T + bias) + residual; row strides in elements; M <= 2048, N <= 8192, K % 8 == 0
+ *   psalm_gemm_f32_rows_pair   psalm_gemm_f32_pair with M <= 2048
+ *   psalm_gemm_f32_grouped     count <= 16 problems C_i (M_i, N_i) = A_i (M_i, K) . W_i (N_i, K)^T in one launch: HOST arrays of device pointers and
+ *                              sizes, contiguous rows, M_i <= 192, N_i <= 8192; a problem with M_i = 0 or N_i = 0 is skipped */
+int psalm_gemm_f32_rows(const float* A, long lda, const float* W, long ldw, const float* bias, const float* residual, long ldr, float* C, long ldc,
+                        int M, int N, int K, int act, void* stream);
+int psalm_gemm_f32_rows_pair(const float* A0, const float* W0, const float* bias0, float* C0, int M0, int N0, int K0, int act0, const float* A1,
+                             const float* W1, const float* bias1, float* C1, int M1, int N1, int K1, int act1, void* stream);
+int psalm_gemm_f32_grouped(const float* const* A_host, const float* const* W_host, float* const* C_host, const int* M_host, const int* N_host, int K,
+                           int count, void* stream);
 /* SwinTransformerBlock.forward front half (swin_trans.py:206-225): norm1 -> zero-pad to a multiple of ws ->
  * roll(-shift) -> window_partition.  x (B*H*W,C) -> out (B*nW*ws*ws, C). */
 int psalm_swin_window_gather(const void* x, int x_dtype, void* out, int out_dtype, const float* gamma,
@@ -637,6 +658,20 @@ int psalm_predictor_forward(const psalm_pr_desc* d, const float* const* ms_host,
                             const float* mask_features, int H2, int W2, const float* seg_query, const float* class_emb, int n_cls, const float* seg_emb,
                             int n_seg, const float* region_emb, int n_reg, float* pred_masks, float* cls_logits, float* seg_logits, float* region_logits,
                             void* workspace, long workspace_bytes, void* gemm_workspace, long gemm_workspace_bytes, int kv_ready, void* stream);
+/* psalm_predictor_forward(kv_ready = 1) for 1 <= B <= 16 prompts of ONE image as one pass over B * Q query rows.  kv_front: the workspace
+ * psalm_predictor_kv wrote (its first psalm_predictor_kv_bytes() bytes are read, nothing is written; any region count).  seg_query (B*Q, D);
+ * class_emb / seg_emb / region_emb: the prompts' embeddings packed in prompt order with (B + 1) HOST offsets each (from 0, not decreasing; <= 8192
+ * class / SEG embeddings and <= 192 regions per prompt), NULL = head absent.  Outputs: pred_masks (B*Q, H2*W2); cls_logits / seg_logits: prompt
+ * b's (Q, n_b) block behind the blocks of the prompts before it; region_logits: its (n_b, Q) block likewise.  Prompt b's words are those
+ * psalm_predictor_forward returns for it alone (same descriptor, K / V front and tuning switches).
+ * workspace: psalm_predictor_forward_batched_workspace() bytes, 256-byte aligned. */
+long psalm_predictor_kv_bytes(const psalm_pr_desc* d, const int* hw_levels_host, int H2, int W2);
+long psalm_predictor_forward_batched_workspace(const psalm_pr_desc* d, const int* hw_levels_host, int H2, int W2, int B, int n_reg_total);
+int psalm_predictor_forward_batched(const psalm_pr_desc* d, const int* hw_levels_host, const void* kv_front, const float* mask_features, int H2, int W2,
+                                    int B, const float* seg_query, const float* class_emb, const int* cls_off_host, const float* seg_emb,
+                                    const int* seg_off_host, const float* region_emb, const int* reg_off_host, float* pred_masks, float* cls_logits,
+                                    float* seg_logits, float* region_logits, void* workspace, long workspace_bytes, void* gemm_workspace,
+                                    long gemm_workspace_bytes, void* stream);
 
 
 /* psalm_postprocess: llava_phi.py:1401-1466 for ONE image from native code -- the mask logits up-sampled to the padded image size (LP:1401-1406),

@@ -1616,7 +1616,8 @@ struct MhaF32Tiles {
     }
 };
 
-template <int NQT>
+// SH (psalm_mha_attention_f32_shared): the B query sets attend ONE K / V (batch stride 0); masks, flags, outputs and partial states stay per b
+template <int NQT, bool SH = false>
 __global__ void __launch_bounds__(64) mha_attention_f32_mfma_kernel(const float* __restrict__ Q, long ldq, const float* __restrict__ K, long ldk,
                                                                     const float* __restrict__ V, long ldv, float* __restrict__ O, long ldo,
                                                                     const unsigned char* __restrict__ mask,
@@ -1639,7 +1640,8 @@ __global__ void __launch_bounds__(64) mha_attention_f32_mfma_kernel(const float*
 #pragma unroll
             for (int i = 0; i < KT * (HD / 4) / 64; ++i) {
                 const int e = lane + 64 * i, r = e >> 3, c4 = (e & 7) * 4;
-                const long row = (long)b * Lk + min(kb + r, Lk - 1);
+                long row = min(kb + r, Lk - 1);
+                if constexpr (!SH) row += (long)b * Lk;
                 kt_[i] = *reinterpret_cast<const f32x4*>(K + row * ldk + h * HD + c4);
                 vt_[i] = *reinterpret_cast<const f32x4*>(V + row * ldv + h * HD + c4);
             }
@@ -1662,18 +1664,32 @@ __global__ void __launch_bounds__(64) mha_attention_f32_mfma_kernel(const float*
 // 100 x 100 self-attention is 16 wavefronts on the whole chip).  Here the same grid (splits, heads, B), but a block is NW wavefronts and
 // wavefront w owns query tile w alone.  The block stages each 64-key K / V tile once, all 64 * NW threads together, into one of TWO LDS
 // buffers: tile i + 1's global loads are issued before tile i's products and stored after them -- one block barrier per tile.
-template <int NW>
-__global__ void __launch_bounds__(64 * NW) mha_attention_f32_qtile_kernel(const float* __restrict__ Q, long ldq, const float* __restrict__ K, long ldk,
-                                                                         const float* __restrict__ V, long ldv, float* __restrict__ O, long ldo,
-                                                                         const unsigned char* __restrict__ mask,
-                                                                         const unsigned char* __restrict__ row_all_masked, float* __restrict__ part,
-                                                                         int Lq, int Lk, int heads, int splits, int chunk, float scale) {
+// SH (psalm_mha_attention_f32_shared): the nb query sets attend ONE K / V (batch stride 0).  A block then holds the query tiles of G of them
+// (grid z = cdiv(nb, G); wavefront w: set blockIdx.z * G + w / NW, tile w % NW) and stages each K / V tile ONCE for all of them -- the staged
+// tile, the key order and every wavefront's instructions are those of the G = 1 form, so the words are.  A block's surplus wavefronts (odd nb)
+// walk the last set again for the barriers' sake and store nothing.
+template <int NW, int G = 1, bool SH = false>
+__global__ void __launch_bounds__(64 * NW * G) mha_attention_f32_qtile_kernel(const float* __restrict__ Q, long ldq, const float* __restrict__ K, long ldk,
+                                                                             const float* __restrict__ V, long ldv, float* __restrict__ O, long ldo,
+                                                                             const unsigned char* __restrict__ mask,
+                                                                             const unsigned char* __restrict__ row_all_masked, float* __restrict__ part,
+                                                                             int Lq, int Lk, int heads, int splits, int chunk, float scale, int nb) {
+    static_assert(G == 1 || SH, "several query sets per block only over a shared K / V");
     typedef float f32x4 __attribute__((ext_vector_type(4)));
-    constexpr int HD = 32, LS = HD + 4, KT = 64, NT = 64 * NW, NE = KT * (HD / 4), NL = (NE + NT - 1) / NT;   // NE float4 per operand tile, NL per thread
+    constexpr int HD = 32, LS = HD + 4, KT = 64, NT = 64 * NW * G, NE = KT * (HD / 4), NL = (NE + NT - 1) / NT;   // NE float4 per operand tile, NL per thread
     __shared__ __attribute__((aligned(16))) float Ks[2][KT * LS];
     __shared__ __attribute__((aligned(16))) float Vs[2][KT * LS];
-    const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
-    const int sp = blockIdx.x, h = blockIdx.y, b = blockIdx.z;
+    const int tid = threadIdx.x, lane = tid & 63;
+    int w = tid >> 6, b = blockIdx.z;
+    bool live = true;
+    if constexpr (G > 1) {
+        const int g = w / NW;
+        w -= g * NW;
+        b = b * G + g;
+        live = b < nb;
+        b = min(b, nb - 1);
+    }
+    const int sp = blockIdx.x, h = blockIdx.y;
     const int k_lo = sp * chunk, k_hi = min(Lk, k_lo + chunk);
     f32x4 kt_[NL], vt_[NL];
     auto fetch = [&](int kb) {                                            // rows past Lk: clamped, masked in the products
@@ -1681,7 +1697,8 @@ __global__ void __launch_bounds__(64 * NW) mha_attention_f32_qtile_kernel(const 
         for (int i = 0; i < NL; ++i) {
             const int e = tid + NT * i, r = e >> 3, c4 = (e & 7) * 4;
             if (NE % NT == 0 || e < NE) {
-                const long row = (long)b * Lk + min(kb + r, Lk - 1);
+                long row = min(kb + r, Lk - 1);
+                if constexpr (!SH) row += (long)b * Lk;
                 kt_[i] = *reinterpret_cast<const f32x4*>(K + row * ldk + h * HD + c4);
                 vt_[i] = *reinterpret_cast<const f32x4*>(V + row * ldv + h * HD + c4);
             }
@@ -1711,7 +1728,7 @@ __global__ void __launch_bounds__(64 * NW) mha_attention_f32_qtile_kernel(const 
         st.key_tile(Ks[buf], Vs[buf], mask, kb, k_hi, Lk);
         if (more) park(buf ^ 1);
     }
-    st.store(O, ldo, part, b, h, sp, Lq, heads, splits);
+    if (G == 1 || live) st.store(O, ldo, part, b, h, sp, Lq, heads, splits);
 }
 
 // merge of the key chunks: thread = (b, h, q, d); weights e^(m_s - M)
@@ -1795,7 +1812,7 @@ extern "C" int psalm_mha_attention_f32(const float* q, long ldq, const float* k,
 #define MHA_F32_LAUNCH(N_)                                                                                                                          \
     do {                                                                                                                                            \
         if (qtile) hipLaunchKernelGGL((mha_attention_f32_qtile_kernel<N_>), grid, dim3(64 * N_), 0, s, q, ldq, k, ldk, v, ldv, out, ldo, mask,      \
-                                      row_all_masked, (float*)workspace, Lq, Lk, heads, splits, chunk, scale);                                      \
+                                      row_all_masked, (float*)workspace, Lq, Lk, heads, splits, chunk, scale, B);                                   \
         else hipLaunchKernelGGL((mha_attention_f32_mfma_kernel<N_>), grid, dim3(64), 0, s, q, ldq, k, ldk, v, ldv, out, ldo, mask, row_all_masked,  \
                                 (float*)workspace, Lq, Lk, heads, splits, chunk, scale);                                                            \
     } while (0)
@@ -1815,6 +1832,59 @@ extern "C" int psalm_mha_attention_f32(const float* q, long ldq, const float* k,
     }
     PSALM_LAUNCH_END("psalm_mha_attention_f32");
 }
+
+// ---- B query sets against ONE K / V: the prompts of an image session in the mask decoder's cross-attention (psalm_predictor_forward_batched).
+// q (B*Lq, ..), mask (B*Lq, Lk), row_all_masked (B*Lq), out (B*Lq, ..) per set; k / v (Lk, ..) once.  The key chunk is that of a B = 1 call
+// of psalm_mha_attention_f32 WHATEVER B is (mha_f32_chunk grows with B: another merge order of the chunks), so set b's output words -- and
+// its partial states, workspace + b * heads * splits * Lq * 36 floats -- are those of that call on set b alone.  With the query-tile form a
+// block holds the tiles of two sets and stages K / V once for both (SHARED_G): half the L2 reads of the G = 1 grid.
+static constexpr int MHA_SHARED_G = 2;
+extern "C" long psalm_mha_attention_f32_shared_workspace(int B, int heads, int Lq, int Lk) {
+    const int splits = cdiv(Lk, mha_f32_chunk(1, heads, Lk));
+    return splits > 1 ? (long)B * heads * splits * Lq * 36 * (long)sizeof(float) : 0;
+}
+extern "C" int psalm_mha_attention_f32_shared(const float* q, long ldq, const float* k, long ldk, const float* v, long ldv, float* out, long ldo,
+                                              const unsigned char* mask, const unsigned char* row_all_masked, void* workspace, int B, int Lq,
+                                              int Lk, int heads, int head_dim, void* stream) {
+    PSALM_CHECK_ARG(head_dim == 32, "psalm_mha_attention_f32_shared: head_dim must be 32");
+    PSALM_CHECK_ARG(Lq >= 1 && Lq <= 128, "psalm_mha_attention_f32_shared: 1 <= Lq <= 128");
+    PSALM_CHECK_ARG(B >= 0 && B <= 65535 && heads >= 1 && Lk >= 0, "psalm_mha_attention_f32_shared: 0 <= B <= 65535, heads >= 1");
+    PSALM_CHECK_ARG(ldq % 4 == 0 && ldk % 4 == 0 && ldv % 4 == 0 && ldo % 4 == 0 && (uintptr_t)q % 16 == 0 && (uintptr_t)k % 16 == 0 &&
+                        (uintptr_t)v % 16 == 0 && (uintptr_t)out % 16 == 0, "psalm_mha_attention_f32_shared: 16-byte aligned rows");
+    if (B == 0 || Lk == 0) return 0;
+    const int chunk = mha_f32_chunk(1, heads, Lk);
+    const int splits = cdiv(Lk, chunk);
+    PSALM_CHECK_ARG(splits == 1 || workspace != nullptr, "psalm_mha_attention_f32_shared: workspace required when the keys are split");
+    const float scale = 1.0f / sqrtf((float)head_dim);
+    const int nqt = cdiv(Lq, 16);
+    hipStream_t s = (hipStream_t)stream;
+    constexpr int G = MHA_SHARED_G;
+#define MHA_F32_LAUNCH(N_)                                                                                                                          \
+    do {                                                                                                                                            \
+        if (qtile) hipLaunchKernelGGL((mha_attention_f32_qtile_kernel<N_, G, true>), dim3(splits, heads, cdiv(B, G)), dim3(64 * N_ * G), 0, s, q,  \
+                                      ldq, k, ldk, v, ldv, out, ldo, mask, row_all_masked, (float*)workspace, Lq, Lk, heads, splits, chunk, scale, \
+                                      B);                                                                                                           \
+        else hipLaunchKernelGGL((mha_attention_f32_mfma_kernel<N_, true>), dim3(splits, heads, B), dim3(64), 0, s, q, ldq, k, ldk, v, ldv, out,    \
+                                ldo, mask, row_all_masked, (float*)workspace, Lq, Lk, heads, splits, chunk, scale);                                 \
+    } while (0)
+    const bool qtile = psalm_get_tuning(PSALM_TUNE_MHA_QTILE_WAVES) != 0;
+    if (nqt <= 1) MHA_F32_LAUNCH(1);
+    else if (nqt <= 2) MHA_F32_LAUNCH(2);
+    else if (nqt <= 4) MHA_F32_LAUNCH(4);
+    else if (nqt <= 7) MHA_F32_LAUNCH(7);
+    else MHA_F32_LAUNCH(8);
+#undef MHA_F32_LAUNCH
+    if (splits > 1 && splits <= 256) {
+        hipLaunchKernelGGL(mha_f32_combine_lds_kernel, dim3(cdiv(Lq, 8), heads, B), dim3(256), 0, s, (const float*)workspace, out, ldo, B, Lq, heads, splits);
+    } else if (splits > 1) {
+        const long total = (long)B * heads * Lq * 32;
+        hipLaunchKernelGGL(mha_f32_combine_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, s, (const float*)workspace, out, ldo, B, Lq,
+                           heads, splits);
+    }
+    PSALM_LAUNCH_END("psalm_mha_attention_f32_shared");
+}
+// the key chunk of psalm_mha_attention_f32 for these sizes (stages.hip pins the decoder's batched self-attention to the B = 1 merge order with it)
+int mha_f32_chunk_of(int B, int heads, int Lk) { return mha_f32_chunk(B, heads, Lk); }
 
 // ============================================================================================ attention-mask generation
 // masks (B*Q, h, w) f32 logits -> bilinear (align_corners=False, PyTorch index rule) to (Ht,Wt) -> mask = logit < 0

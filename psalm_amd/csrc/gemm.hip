@@ -1816,6 +1816,22 @@ __global__ void __launch_bounds__(64 * NWV) gemm_f32_skinny_pair_kernel(GemmArgs
     if ((int)blockIdx.x * 32 >= g.N || (int)blockIdx.y * 32 >= g.M) return;      // (block-uniform)
     gemm_f32_skinny_body<TC, NWV>(g, part, blockIdx.x, blockIdx.y);
 }
+// Up to 16 independent skinny problems of one K in ONE launch (blockIdx.z picks the problem from a table in the kernel arguments; contiguous
+// operand rows, no bias): the ragged last products of the mask decoder's heads over the prompts of a session (psalm_predictor_forward_batched)
+// -- class logits (Q, n_cls[b]), SEG logits (Q, n_seg[b]), region logits (n_reg[b], Q).  Same body, same words as one psalm_gemm each.
+struct GemmGroup { const float* A[16]; const float* W[16]; float* C[16]; int M[16]; int N[16]; int K; };
+template <typename TC, int NWV>
+__global__ void __launch_bounds__(64 * NWV) gemm_f32_skinny_group_kernel(GemmGroup t) {
+    __shared__ float part[NWV][32 * 32];
+    const int z = blockIdx.z;
+    GemmArgs g;
+    g.A = t.A[z]; g.W = t.W[z]; g.bias = nullptr; g.res = nullptr; g.C = t.C[z];
+    g.M = t.M[z]; g.N = t.N[z]; g.K = t.K; g.act = 0; g.act_col_start = 0;
+    g.lda = g.K; g.ldw = g.K; g.ldr = 0; g.ldc = g.N;
+    g.tiles_m = g.tiles_n = 0; g.row_fast = 0;
+    if ((int)blockIdx.x * 32 >= g.N || (int)blockIdx.y * 32 >= g.M) return;      // (block-uniform)
+    gemm_f32_skinny_body<TC, NWV>(g, part, blockIdx.x, blockIdx.y);
+}
 
 // (r06: the process-wide tuning words below are atomics -- a test or `--gemm-policy` flipping one while another host thread (PSALM.replica) launches
 //  gives that thread's next launch the old or the new value, never a torn one)
@@ -2011,10 +2027,15 @@ extern "C" int psalm_layernorm(const void* x, int x_dtype, long ldx, void* y, in
                                const float* gamma, const float* beta, int rows, int C, float eps, void* stream);
 
 static int launch_fast(GemmArgs g, GemmFastArgs fa, bool conv, int c_dtype, void* workspace, long workspace_bytes, hipStream_t s,
-                       const LnEpilogue* ln = nullptr, bool x3 = false) {
-    const int M = g.M, N = g.N, K = g.K;
+                       const LnEpilogue* ln = nullptr, bool x3 = false, int select_m = 0) {
+    // select_m (internal, gemm_x3_select_rows): the kernel form -- tiles, K loop, split-K -- is chosen as for a problem of select_m rows; the grid covers g.M
+    const int Mg = g.M, M = select_m > 0 ? select_m : g.M, N = g.N, K = g.K;
     int BM, BN, splits;
     select_fast_config(M, N, K, workspace != nullptr, workspace_bytes, BM, BN, splits, x3);
+    if (select_m > 0 && splits > 1 && (long)splits * Mg * N * 4 > workspace_bytes) {      // (fewer K slices would be another sum order)
+        psalm_set_error("psalm_gemm_x3: split-K workspace too small for the rows of this call under the selected form");
+        return -1;
+    }
     if (fa.so) splits = 1;                                        // split-f16 output is written by the GEMM epilogue itself: no split-K
     int kps = splits > 1 ? cdiv(cdiv(K, 64), splits) * 64 : K;
     const int x3s = g_x3_slice.load();
@@ -2057,7 +2078,7 @@ static int launch_fast(GemmArgs g, GemmFastArgs fa, bool conv, int c_dtype, void
         else mid = 0;
         if (mid) {
             slice = 3;
-            if (msplit > 1 && workspace && !fa.so && (long)msplit * M * N * 4 <= workspace_bytes) splits = msplit;
+            if (msplit > 1 && workspace && !fa.so && (long)msplit * Mg * N * 4 <= workspace_bytes) splits = msplit;
         }
     }
     if (slice) {                                                  // slice form: the kernel's K loop runs over the true (padded) K = Kp
@@ -2065,9 +2086,9 @@ static int launch_fast(GemmArgs g, GemmFastArgs fa, bool conv, int c_dtype, void
         kps = splits > 1 ? cdiv(cdiv(g.K, 64), splits) * 64 : g.K;
         splits = cdiv(g.K, kps);
     }
-    g.tiles_m = cdiv(M, BM);
+    g.tiles_m = cdiv(Mg, BM);
     g.tiles_n = cdiv(N, BN);
-    g.row_fast = N > M ? 1 : 0;                                  // the larger operand's tiles stay in one XCD's L2
+    g.row_fast = N > Mg ? 1 : 0;                                  // the larger operand's tiles stay in one XCD's L2
     const long tiles = (long)g.tiles_m * g.tiles_n;
     fa.g = g;
     fa.k_per_split = kps;
@@ -2189,7 +2210,7 @@ static int launch_fast(GemmArgs g, GemmFastArgs fa, bool conv, int c_dtype, void
     else if (ln) also(ln->split_out ? "layernorm_split_kernel" : "layernorm_vec_kernel");
     if (splits > 1) {
         if (ln && ln->split_out) {                                // ... + the normalised rows in split-f16 form (psalm_gemm_x3_ln_split)
-#define RLNS_LAUNCH(NV_) hipLaunchKernelGGL((splitk_reduce_ln_kernel<float, NV_, true>), dim3(M), dim3(256), 0, s, g, (const float*)workspace, splits, \
+#define RLNS_LAUNCH(NV_) hipLaunchKernelGGL((splitk_reduce_ln_kernel<float, NV_, true>), dim3(Mg), dim3(256), 0, s, g, (const float*)workspace, splits, \
                                             ln->gamma, ln->beta, ln->eps, (float*)ln->out, ln->ld, (unsigned short*)ln->split_out, ln->split_inv, N)
             const int nv = N <= 1024 ? 1 : (N <= 2048 ? 2 : (N <= 4096 ? 4 : 8));
             if (nv == 1) RLNS_LAUNCH(1); else if (nv == 2) RLNS_LAUNCH(2); else if (nv == 4) RLNS_LAUNCH(4); else RLNS_LAUNCH(8);
@@ -2197,7 +2218,7 @@ static int launch_fast(GemmArgs g, GemmFastArgs fa, bool conv, int c_dtype, void
             PSALM_LAUNCH_END("psalm_gemm_x3_ln_split");
         }
         if (ln) {                                                 // reduce + epilogue + LayerNorm in one pass (fp32 C, checked by the caller)
-#define RLN_LAUNCH(TL_, NV_) hipLaunchKernelGGL((splitk_reduce_ln_kernel<TL_, NV_>), dim3(M), dim3(256), 0, s, g, (const float*)workspace, splits, \
+#define RLN_LAUNCH(TL_, NV_) hipLaunchKernelGGL((splitk_reduce_ln_kernel<TL_, NV_>), dim3(Mg), dim3(256), 0, s, g, (const float*)workspace, splits, \
                                                 ln->gamma, ln->beta, ln->eps, (TL_*)ln->out, ln->ld)
             const int nv = N <= 1024 ? 1 : (N <= 2048 ? 2 : (N <= 4096 ? 4 : 8));       // 4-column vectors per thread
             if (ln->dtype == PSALM_F32) {
@@ -2209,7 +2230,7 @@ static int launch_fast(GemmArgs g, GemmFastArgs fa, bool conv, int c_dtype, void
             PSALM_LAUNCH_END("psalm_gemm_ln");
         }
         const long n4 = (N + 3) / 4;
-        const dim3 rgrid((unsigned)(((long)M * n4 + 255) / 256));
+        const dim3 rgrid((unsigned)(((long)Mg * n4 + 255) / 256));
         if (c_dtype == PSALM_F32) hipLaunchKernelGGL((splitk_reduce_kernel<float>), rgrid, dim3(256), 0, s, g, (const float*)workspace, splits);
         else hipLaunchKernelGGL((splitk_reduce_kernel<bf16_t>), rgrid, dim3(256), 0, s, g, (const float*)workspace, splits);
     }
@@ -2217,9 +2238,9 @@ static int launch_fast(GemmArgs g, GemmFastArgs fa, bool conv, int c_dtype, void
         hipError_t e = hipGetLastError();
         if (e != hipSuccess) { psalm_set_error("psalm_gemm_ln: GEMM launch failed"); return (int)e; }
         if (ln->split_out)
-            return psalm_layernorm_split((const float*)g.C, g.ldc, (float*)ln->out, ln->ld, ln->gamma, ln->beta, M, N, ln->eps, ln->split_out,
+            return psalm_layernorm_split((const float*)g.C, g.ldc, (float*)ln->out, ln->ld, ln->gamma, ln->beta, Mg, N, ln->eps, ln->split_out,
                                          ln->split_inv, nullptr, 0, nullptr, nullptr, (void*)s);
-        return psalm_layernorm(g.C, PSALM_F32, g.ldc, ln->out, ln->dtype, ln->ld, nullptr, 0, ln->gamma, ln->beta, M, N, ln->eps, (void*)s);
+        return psalm_layernorm(g.C, PSALM_F32, g.ldc, ln->out, ln->dtype, ln->ld, nullptr, 0, ln->gamma, ln->beta, Mg, N, ln->eps, (void*)s);
     }
     PSALM_LAUNCH_END("psalm_gemm");
 }
@@ -2338,12 +2359,14 @@ extern "C" int psalm_gemm(const void* A, int a_dtype, long lda, const void* W, i
 
 // Two exact-fp32 skinny GEMMs (psalm_gemm with float32 operands, M <= 192, N <= 8192, K % 8 == 0) as one launch:
 // C_i = act_i(A_i . W_i^T + bias_i), i = 0, 1; contiguous operand rows (row strides K / N).  See gemm_f32_skinny_pair_kernel.
-extern "C" int psalm_gemm_f32_pair(const float* A0, const float* W0, const float* bias0, float* C0, int M0, int N0, int K0, int act0,
-                                   const float* A1, const float* W1, const float* bias1, float* C1, int M1, int N1, int K1, int act1, void* stream) {
+// (max_m: 192 for psalm_gemm_f32_pair -- the range in which psalm_gemm takes the same kernel -- 16 * 128 for psalm_gemm_f32_rows_pair)
+static int gemm_f32_pair_impl(const float* A0, const float* W0, const float* bias0, float* C0, int M0, int N0, int K0, int act0,
+                              const float* A1, const float* W1, const float* bias1, float* C1, int M1, int N1, int K1, int act1, void* stream, int max_m) {
     PSALM_CHECK_ARG(A0 && W0 && C0 && A1 && W1 && C1, "psalm_gemm_f32_pair: null operand");
-    PSALM_CHECK_ARG(M0 > 0 && M1 > 0 && M0 <= 192 && M1 <= 192 && N0 > 0 && N1 > 0 && N0 <= 8192 && N1 <= 8192 && K0 > 0 && K1 > 0 && K0 % 8 == 0 && K1 % 8 == 0 &&
+    PSALM_CHECK_ARG(M0 > 0 && M1 > 0 && M0 <= max_m && M1 <= max_m && N0 > 0 && N1 > 0 && N0 <= 8192 && N1 <= 8192 && K0 > 0 && K1 > 0 && K0 % 8 == 0 && K1 % 8 == 0 &&
                         (K0 >= 256) == (K1 >= 256),
-                    "psalm_gemm_f32_pair: M <= 192, N <= 8192, K % 8 == 0, both K below or both from 256 (psalm_gemm's 4- / 16-wave skinny kernels)");
+                    max_m == 192 ? "psalm_gemm_f32_pair: M <= 192, N <= 8192, K % 8 == 0, both K below or both from 256 (psalm_gemm's 4- / 16-wave skinny kernels)"
+                                 : "psalm_gemm_f32_rows_pair: M <= 2048, N <= 8192, K % 8 == 0, both K below or both from 256 (psalm_gemm's 4- / 16-wave skinny kernels)");
     PSALM_CHECK_ARG((uintptr_t)A0 % 16 == 0 && (uintptr_t)W0 % 16 == 0 && (uintptr_t)A1 % 16 == 0 && (uintptr_t)W1 % 16 == 0, "psalm_gemm_f32_pair: 16-byte aligned operands");
     PSALM_CHECK_ARG(!((act0 | act1) & (ACT_BIAS_ROW | ACT_POST_RESIDUAL)), "psalm_gemm_f32_pair: plain activations only");
     GemmArgs g[2];
@@ -2360,6 +2383,63 @@ extern "C" int psalm_gemm_f32_pair(const float* A0, const float* W0, const float
     if (K0 >= 256) hipLaunchKernelGGL((gemm_f32_skinny_pair_kernel<float, 16>), grid, dim3(1024), 0, (hipStream_t)stream, g[0], g[1]);
     else hipLaunchKernelGGL((gemm_f32_skinny_pair_kernel<float, 4>), grid, dim3(256), 0, (hipStream_t)stream, g[0], g[1]);
     PSALM_LAUNCH_END("psalm_gemm_f32_pair");
+}
+extern "C" int psalm_gemm_f32_pair(const float* A0, const float* W0, const float* bias0, float* C0, int M0, int N0, int K0, int act0,
+                                   const float* A1, const float* W1, const float* bias1, float* C1, int M1, int N1, int K1, int act1, void* stream) {
+    return gemm_f32_pair_impl(A0, W0, bias0, C0, M0, N0, K0, act0, A1, W1, bias1, C1, M1, N1, K1, act1, stream, 192);
+}
+
+// ---- the exact-fp32 skinny kernel over MANY row tiles: the B * Q query rows of a session's prompts (psalm_predictor_forward_batched).
+// gemm_f32_skinny_body computes an output element from its A row, its W row and K alone (the wave split of K follows K and the 4- / 16-wave
+// choice, which follows K as in psalm_gemm), so row r of an M-row call carries the words psalm_gemm (float32 operands, M <= 192) returns for
+// any row set holding it -- whatever the 32-row tile boundaries.  psalm_gemm's own dispatch (register-staged kernel above 192 rows) is unchanged.
+//   psalm_gemm_f32_rows        C = act(A . W^T + bias) + residual; fp32, row strides in elements, M <= 16 * 128, N <= 8192, K % 8 == 0
+//   psalm_gemm_f32_rows_pair   psalm_gemm_f32_pair with M <= 16 * 128
+//   psalm_gemm_f32_grouped     count <= 16 problems C_i (M_i, N_i) = A_i (M_i, K) . W_i (N_i, K)^T, contiguous rows, M_i <= 192, one launch
+//                              (HOST arrays of device pointers / sizes; a problem with M_i = 0 or N_i = 0 is skipped)
+extern "C" int psalm_gemm_f32_rows(const float* A, long lda, const float* W, long ldw, const float* bias, const float* residual, long ldr, float* C,
+                                   long ldc, int M, int N, int K, int act, void* stream) {
+    if (M == 0 || N == 0) return 0;
+    PSALM_CHECK_ARG(A && W && C, "psalm_gemm_f32_rows: null operand");
+    PSALM_CHECK_ARG(M > 0 && M <= 16 * 128 && N > 0 && N <= 8192 && K > 0 && K % 8 == 0, "psalm_gemm_f32_rows: M <= 2048, N <= 8192, K % 8 == 0");
+    PSALM_CHECK_ARG((uintptr_t)A % 16 == 0 && lda % 4 == 0 && (uintptr_t)W % 16 == 0 && ldw % 4 == 0, "psalm_gemm_f32_rows: 16-byte aligned operand rows");
+    GemmArgs g;
+    g.A = A; g.W = W; g.bias = bias; g.res = residual; g.C = C;
+    g.lda = lda; g.ldw = ldw; g.ldr = ldr; g.ldc = ldc;
+    g.M = M; g.N = N; g.K = K; g.act = act; g.act_col_start = 0;
+    g.tiles_m = g.tiles_n = 0; g.row_fast = 0;
+    const dim3 grid(cdiv(N, 32), cdiv(M, 32));
+    snprintf(g_last_kernel, sizeof(g_last_kernel), "gemm_f32_skinny_kernel<float, %d>", K >= 256 ? 16 : 4);
+    if (K >= 256) hipLaunchKernelGGL((gemm_f32_skinny_kernel<float, 16>), grid, dim3(1024), 0, (hipStream_t)stream, g);
+    else hipLaunchKernelGGL((gemm_f32_skinny_kernel<float, 4>), grid, dim3(256), 0, (hipStream_t)stream, g);
+    PSALM_LAUNCH_END("psalm_gemm_f32_rows");
+}
+extern "C" int psalm_gemm_f32_rows_pair(const float* A0, const float* W0, const float* bias0, float* C0, int M0, int N0, int K0, int act0,
+                                        const float* A1, const float* W1, const float* bias1, float* C1, int M1, int N1, int K1, int act1, void* stream) {
+    return gemm_f32_pair_impl(A0, W0, bias0, C0, M0, N0, K0, act0, A1, W1, bias1, C1, M1, N1, K1, act1, stream, 16 * 128);
+}
+extern "C" int psalm_gemm_f32_grouped(const float* const* A_host, const float* const* W_host, float* const* C_host, const int* M_host, const int* N_host,
+                                      int K, int count, void* stream) {
+    PSALM_CHECK_ARG(A_host && W_host && C_host && M_host && N_host, "psalm_gemm_f32_grouped: null argument");
+    PSALM_CHECK_ARG(count >= 1 && count <= 16 && K > 0 && K % 8 == 0, "psalm_gemm_f32_grouped: 1 <= count <= 16, K % 8 == 0");
+    GemmGroup t;
+    int mm = 0, mn = 0;
+    for (int i = 0; i < 16; ++i) {
+        const bool on = i < count && M_host[i] > 0 && N_host[i] > 0;
+        if (i < count) PSALM_CHECK_ARG(M_host[i] >= 0 && M_host[i] <= 192 && N_host[i] >= 0 && N_host[i] <= 8192, "psalm_gemm_f32_grouped: M <= 192, N <= 8192 per problem");
+        if (on) PSALM_CHECK_ARG(A_host[i] && W_host[i] && C_host[i] && (uintptr_t)A_host[i] % 16 == 0 && (uintptr_t)W_host[i] % 16 == 0,
+                                "psalm_gemm_f32_grouped: 16-byte aligned operands");
+        t.A[i] = on ? A_host[i] : nullptr; t.W[i] = on ? W_host[i] : nullptr; t.C[i] = on ? C_host[i] : nullptr;
+        t.M[i] = on ? M_host[i] : 0; t.N[i] = on ? N_host[i] : 0;
+        mm = std::max(mm, t.M[i]); mn = std::max(mn, t.N[i]);
+    }
+    t.K = K;
+    if (mm == 0) return 0;
+    const dim3 grid(cdiv(mn, 32), cdiv(mm, 32), count);
+    snprintf(g_last_kernel, sizeof(g_last_kernel), "gemm_f32_skinny_group_kernel<float, %d>", K >= 256 ? 16 : 4);
+    if (K >= 256) hipLaunchKernelGGL((gemm_f32_skinny_group_kernel<float, 16>), grid, dim3(1024), 0, (hipStream_t)stream, t);
+    else hipLaunchKernelGGL((gemm_f32_skinny_group_kernel<float, 4>), grid, dim3(256), 0, (hipStream_t)stream, t);
+    PSALM_LAUNCH_END("psalm_gemm_f32_grouped");
 }
 
 // psalm_gemm followed by LayerNorm over the N columns of the (fp32) result:  C as psalm_gemm,  ln_out = LN(C) * gamma + beta
@@ -2527,7 +2607,7 @@ struct SplitOut { void* so; long ldso; int so_kp, so_col_off, so_col_start, so_g
 static int gemm_x3_impl(const void* A2, long lda, const float* a_scale, const void* W2, long ldw, const float* w_scale, int Kp,
                         const float* bias, const void* residual, long ldr, void* C, long ldc, int M, int N, int act,
                         int act_col_start, void* workspace, long workspace_bytes, void* stream, const SplitOut* so, const char* name,
-                        const LnEpilogue* ln = nullptr) {
+                        const LnEpilogue* ln = nullptr, int select_m = 0) {
     if (M == 0 || N == 0) return 0;
     PSALM_CHECK_ARG(Kp > 0 && Kp % 64 == 0, "psalm_gemm_x3: Kp must be a positive multiple of 64");
     PSALM_CHECK_ARG((uintptr_t)A2 % 16 == 0 && (lda * 2) % 16 == 0 && (uintptr_t)W2 % 16 == 0 && (ldw * 2) % 16 == 0 && lda >= 2L * Kp && ldw >= 2L * Kp,
@@ -2539,7 +2619,7 @@ static int gemm_x3_impl(const void* A2, long lda, const float* a_scale, const vo
     g.M = M; g.N = N; g.K = 3 * Kp; g.act = act; g.act_col_start = act_col_start;
     g.row_fast = 0; g.tiles_m = g.tiles_n = 0;
     hipStream_t s = (hipStream_t)stream;
-    if (!so && !ln && M <= 128 && N <= g_skinny_nmax && !g_tile_policy) {
+    if (!so && !ln && (select_m > 0 ? select_m : M) <= 128 && N <= g_skinny_nmax && !g_tile_policy) {
         const dim3 grid(cdiv(N, 32), cdiv(M, 32));
         g.K = g_x3_products * Kp;                                // (1 product: the first Kp of the K panel = hi.hi)
         snprintf(g_last_kernel, sizeof(g_last_kernel), "gemm_bf16_skinny_kernel<float, true>");
@@ -2556,7 +2636,15 @@ static int gemm_x3_impl(const void* A2, long lda, const float* a_scale, const vo
         fa.so_col_start = so->so_col_start; fa.so_global = so->so_global; fa.so_inv = so->so_inv; fa.so_par = so->so_par;
         fa.so_paired = so->so_paired;
     }
-    return launch_fast(g, fa, false, PSALM_F32, workspace, workspace_bytes, s, ln, true);
+    return launch_fast(g, fa, false, PSALM_F32, workspace, workspace_bytes, s, ln, true, select_m);
+}
+// psalm_gemm_x3 (no bias / residual / activation) whose kernel form is selected as for `select_m` rows while the grid covers M of them: row r
+// then carries the words of a select_m-row call on any row set holding it (every form computes an output element from its A row, its W row
+// and the K order of the form alone).  Internal: the (B * Q, mask_dim) . mask_features^T GEMM of psalm_predictor_forward_batched selects by Q.
+int gemm_x3_select_rows(const void* A2, long lda, const float* a_scale, const void* W2, long ldw, const float* w_scale, int Kp, void* C, long ldc,
+                        int M, int N, int select_m, void* workspace, long workspace_bytes, void* stream) {
+    return gemm_x3_impl(A2, lda, a_scale, W2, ldw, w_scale, Kp, nullptr, nullptr, 0, C, ldc, M, N, 0, 0, workspace, workspace_bytes, stream, nullptr,
+                        "psalm_gemm_x3", nullptr, select_m);
 }
 extern "C" int psalm_gemm_x3(const void* A2, long lda, const float* a_scale, const void* W2, long ldw, const float* w_scale, int Kp,
                              const float* bias, const void* residual, long ldr, void* C, long ldc, int M, int N, int act,

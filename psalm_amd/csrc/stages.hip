@@ -835,6 +835,214 @@ extern "C" int psalm_predictor_forward(const psalm_pr_desc* d, const float* cons
     return 0;
 }
 
+// ================================================================================================= masked-attention decoder, the prompts of ONE image
+//   psalm_predictor_forward_batched   psalm_predictor_forward(kv_ready = 1) for B prompts of one image session as ONE pass over B * Q query rows against
+//                                     the session's one K / V front (psalm_predictor_kv; read, never written).  Nothing in the decoder sums across query
+//                                     rows, so prompt b's outputs are, word for word, those of the per-prompt call -- given that the three places whose
+//                                     arithmetic follows the row count are pinned to the per-prompt form:
+//                                       * cross-attention: psalm_mha_attention_f32_shared (the key chunk of a B = 1 call); self-attention: the batched
+//                                         entry, whose chunk for Lk = Q <= 128 is checked below to be the B = 1 chunk
+//                                       * the exact-fp32 GEMMs of the query rows: psalm_gemm_f32_rows[_pair] / psalm_gemm_f32_grouped (the skinny body
+//                                         psalm_gemm takes for M <= 192, over cdiv(B * Q, 32) row tiles)
+//                                       * the split-f16 mask GEMM: kernel form selected as for Q rows (gemm_x3_select_rows)
+//                                     Same tuning switches, same launch sequence with B * Q rows; one grouped launch per head for the ragged last products.
+int gemm_x3_select_rows(const void* A2, long lda, const float* a_scale, const void* W2, long ldw, const float* w_scale, int Kp, void* C, long ldc,
+                        int M, int N, int select_m, void* workspace, long workspace_bytes, void* stream);      // gemm.hip
+int mha_f32_chunk_of(int B, int heads, int Lk);                                                                // attention.hip
+struct PrBLayout { long dec, me0, me1, me2, mes, mesinv, masks, amask, flags, outq, qp, a, x1, out[2], qk, v, hdd, mha, t0, t1, total; };
+static PrBLayout prb_layout(const psalm_pr_desc* d, const int* hwl, int H2, int W2, int B) {
+    const long D = d->D, R = (long)B * d->Q, HW2 = (long)H2 * W2;
+    long mhw = 0, mmha = 0;
+    for (int l = 0; l < d->num_levels; ++l) {
+        const long hw = (long)hwl[2 * l] * hwl[2 * l + 1];
+        mhw = std::max(mhw, hw);
+        mmha = std::max(mmha, psalm_mha_attention_f32_shared_workspace(B, d->heads, d->Q, (int)hw));
+    }
+    mmha = std::max(mmha, psalm_mha_attention_f32_workspace(B, d->heads, d->Q, d->Q));
+    PrBLayout o;
+    long p = 0;
+    o.dec = p; p += al256(R * D * 4);
+    o.me0 = p; p += al256(R * D * 4); o.me1 = p; p += al256(R * D * 4); o.me2 = p; p += al256(R * std::max<long>(D, d->mask_dim) * 4);
+    o.mes = p; p += al256(R * 2 * c64(d->mask_dim) * 2); o.mesinv = p; p += al256(R * 4);
+    o.masks = p; p += al256(R * HW2 * 4);
+    o.amask = p; p += al256(R * mhw); o.flags = p; p += al256(R);
+    o.outq = p; p += al256(R * D * 4); o.qp = p; p += al256(R * D * 4); o.a = p; p += al256(R * D * 4); o.x1 = p; p += al256(R * D * 4);
+    o.out[0] = p; p += al256(R * D * 4); o.out[1] = p; p += al256(R * D * 4);
+    o.qk = p; p += al256(R * 2 * D * 4); o.v = p; p += al256(R * D * 4);
+    o.hdd = p; p += al256(R * (long)d->ffn * 4);
+    o.mha = p; p += al256(mmha);
+    o.t0 = p; p += al256(R * D * 4); o.t1 = p; p += al256(R * D * 4);
+    o.total = p;
+    return o;
+}
+static int prb_check(const psalm_pr_desc* d, const int* hwl, int H2, int W2, int B) {
+    if (pr_check(d) != 0) return -1;
+    PSALM_CHECK_ARG(hwl && H2 > 0 && W2 > 0, "psalm_predictor_forward_batched: level sizes / mask feature size");
+    PSALM_CHECK_ARG(B >= 1 && B <= 16 && d->Q <= 128, "psalm_predictor_forward_batched: 1 <= B <= 16 prompts, Q <= 128");
+    PSALM_CHECK_ARG(d->ffn <= 8192 && d->D <= 8192 && d->mask_dim <= 8192, "psalm_predictor_forward_batched: widths <= 8192 (the exact-fp32 skinny GEMM)");
+    return 0;
+}
+extern "C" long psalm_predictor_kv_bytes(const psalm_pr_desc* d, const int* hw_levels_host, int H2, int W2) {
+    if (pr_check(d) != 0 || !hw_levels_host || H2 <= 0 || W2 <= 0) return -1;
+    return pr_layout(d, hw_levels_host, H2, W2, 0).dec;          // (the front kin .. mfinv lies before `dec` and does not depend on the region count)
+}
+extern "C" long psalm_predictor_forward_batched_workspace(const psalm_pr_desc* d, const int* hw_levels_host, int H2, int W2, int B, int n_reg_total) {
+    (void)n_reg_total;                                            // (the region embeddings are an operand of the grouped product where they lie: no scratch rows)
+    if (prb_check(d, hw_levels_host, H2, W2, B) != 0) return -1;
+    return prb_layout(d, hw_levels_host, H2, W2, B).total;
+}
+extern "C" int psalm_predictor_forward_batched(const psalm_pr_desc* d, const int* hw_levels_host, const void* kv_front, const float* mask_features, int H2,
+                                               int W2, int B, const float* seg_query, const float* class_emb, const int* cls_off_host,
+                                               const float* seg_emb, const int* seg_off_host, const float* region_emb, const int* reg_off_host,
+                                               float* pred_masks, float* cls_logits, float* seg_logits, float* region_logits, void* workspace,
+                                               long workspace_bytes, void* gemm_workspace, long gemm_workspace_bytes, void* stream) {
+    if (prb_check(d, hw_levels_host, H2, W2, B) != 0) return -1;
+    PSALM_CHECK_ARG(kv_front && mask_features && seg_query && pred_masks && workspace, "psalm_predictor_forward_batched: null argument");
+    PSALM_CHECK_ARG((uintptr_t)kv_front % 256 == 0, "psalm_predictor_forward_batched: kv_front is the 256-byte aligned workspace psalm_predictor_kv wrote");
+    const int D = d->D, Q = d->Q, nh = d->heads, nl = d->num_layers, nlev = d->num_levels, HW2 = H2 * W2, MD = d->mask_dim, F = d->ffn, R = B * Q;
+    const PrLayout kvl = pr_layout(d, hw_levels_host, H2, W2, 0);
+    const PrBLayout lo = prb_layout(d, hw_levels_host, H2, W2, B);
+    PSALM_CHECK_ARG(workspace_bytes >= lo.total && (uintptr_t)workspace % 256 == 0,
+                    "psalm_predictor_forward_batched: workspace of psalm_predictor_forward_batched_workspace() bytes, 256-byte aligned");
+    // self-attention goes through the batched psalm_mha_attention_f32: its key chunk for Lk = Q must be the one a single prompt gets
+    PSALM_CHECK_ARG(mha_f32_chunk_of(B, nh, Q) == mha_f32_chunk_of(1, nh, Q), "psalm_predictor_forward_batched: the self-attention key chunk depends on B for this (heads, Q)");
+    // the ragged heads: (B + 1) offsets each, from 0, not decreasing; a prompt's product must lie in the skinny kernel's range as in the per-prompt call
+    struct HeadIn { const float* emb; const int* off; float* out; const char* what; bool rows_are_emb; };
+    const HeadIn hin[3] = {{class_emb, cls_off_host, cls_logits, "cls", false}, {seg_emb, seg_off_host, seg_logits, "seg", false}, {region_emb, reg_off_host, region_logits, "region", true}};
+    for (const HeadIn& x : hin) {
+        if (!x.emb || !x.off) continue;
+        PSALM_CHECK_ARG(x.off[0] == 0, "psalm_predictor_forward_batched: an offset array starts at 0");
+        for (int b = 0; b < B; ++b) {
+            const int n = x.off[b + 1] - x.off[b];
+            PSALM_CHECK_ARG(n >= 0, "psalm_predictor_forward_batched: offsets do not decrease");
+            PSALM_CHECK_ARG(n <= (x.rows_are_emb ? 192 : 8192), "psalm_predictor_forward_batched: <= 8192 class / SEG embeddings and <= 192 regions per prompt");
+        }
+        PSALM_CHECK_ARG(x.off[B] == 0 || x.out != nullptr, "psalm_predictor_forward_batched: logits output missing");
+        PSALM_CHECK_ARG((uintptr_t)x.emb % 16 == 0, "psalm_predictor_forward_batched: 16-byte aligned embeddings");
+    }
+    const char* kv = (const char*)kv_front;
+    char* ws = (char*)workspace;
+    const float eps = 1e-5f;
+    const float* Kl[3]; const float* Vl[3];
+    for (int l = 0; l < 3; ++l) { Kl[l] = (const float*)(kv + kvl.K[l]); Vl[l] = (const float*)(kv + kvl.V[l]); }
+    const void* mfp = kv + kvl.mfp; const float* mfinv = (const float*)(kv + kvl.mfinv);
+    float* dec = (float*)(ws + lo.dec); float* me0 = (float*)(ws + lo.me0); float* me1 = (float*)(ws + lo.me1); float* me2 = (float*)(ws + lo.me2);
+    void* mes = ws + lo.mes; float* mesinv = (float*)(ws + lo.mesinv);
+    float* masks = (float*)(ws + lo.masks);
+    unsigned char* amask = (unsigned char*)(ws + lo.amask); unsigned char* flags = (unsigned char*)(ws + lo.flags);
+    float* outq = (float*)(ws + lo.outq); float* qp = (float*)(ws + lo.qp); float* a = (float*)(ws + lo.a); float* x1 = (float*)(ws + lo.x1);
+    float* outb[2] = {(float*)(ws + lo.out[0]), (float*)(ws + lo.out[1])};
+    float* qk = (float*)(ws + lo.qk); float* v = (float*)(ws + lo.v); float* hdd = (float*)(ws + lo.hdd);
+    void* mha = ws + lo.mha;
+    float* t0 = (float*)(ws + lo.t0); float* t1 = (float*)(ws + lo.t1);
+    int rc;
+#define PR(call) do { rc = (call); if (rc) return rc; } while (0)
+    // exact-fp32 GEMM of the B * Q query rows: the skinny body of the per-prompt call's psalm_gemm
+    auto g32 = [&](const float* A, int K, const float* W, const float* b, const float* res, float* C, int N, int act) -> int {
+        return psalm_gemm_f32_rows(A, K, W, K, b, res, res ? N : 0, C, N, R, N, K, act, stream);
+    };
+    auto ln = [&](const float* x, const float* g_, const float* b_, float* y) -> int {
+        return psalm_layernorm3(x, PSALM_F32, D, y, PSALM_F32, D, nullptr, 0, nullptr, 0, nullptr, 0, g_, b_, R, D, eps, stream);
+    };
+    const int KpM = c64(MD);
+    int nl_l[3] = {0, 0, 0};
+    for (int l = 0; l < nlev; ++l) nl_l[l] = (nl - l + nlev - 1) / nlev;
+    const bool mf_split = HW2 > 4096;
+    // (the per-prompt call's condition: by Q, not by B * Q)
+    const bool fuse = D % 8 == 0 && D <= 2048 && Q <= 192 && psalm_get_tuning(PSALM_TUNE_DECODER_FUSE) != 0;
+    auto mask_head = [&](const float* out_, bool have_dec, const psalm_pr_layer* next, float* dst) -> int {
+        int r;
+        if (!have_dec && (r = ln(out_, d->dn_g, d->dn_b, dec))) return r;
+        if (fuse && next) {
+            if ((r = psalm_gemm_f32_rows_pair(dec, d->mask_embed_w[0], d->mask_embed_b[0], me0, R, D, D, 1, outq, next->cq_w, next->cq_b, qp, R, D, D, 0, stream))) return r;
+        } else if ((r = g32(dec, D, d->mask_embed_w[0], d->mask_embed_b[0], nullptr, me0, D, 1))) return r;
+        if ((r = g32(me0, D, d->mask_embed_w[1], d->mask_embed_b[1], nullptr, me1, D, 1))) return r;
+        if ((r = g32(me1, D, d->mask_embed_w[2], d->mask_embed_b[2], nullptr, me2, MD, 0))) return r;
+        if (mf_split) {
+            if ((r = psalm_split_f16(me2, MD, mes, 2L * KpM, mesinv, R, MD, stream))) return r;
+            return gemm_x3_select_rows(mes, 2L * KpM, mesinv, mfp, 2L * KpM, mfinv, KpM, dst, HW2, R, HW2, Q, gemm_workspace, gemm_workspace_bytes, stream);
+        }
+        return g32(me2, MD, mask_features, nullptr, nullptr, dst, HW2, 0);
+    };
+    const float* out = seg_query;
+    // (`+ query_embed`: row b * Q + q takes query_embed[q] -- add_rows = Q)
+    if (fuse) PR(psalm_add_bcast(out, PSALM_F32, d->query_embed, PSALM_F32, outq, PSALM_F32, R, D, Q, stream));
+    PR(mask_head(out, false, &d->layers[0], masks));
+    if (!fuse) PR(psalm_add_bcast(out, PSALM_F32, d->query_embed, PSALM_F32, outq, PSALM_F32, R, D, Q, stream));
+    int cur = 0;
+    for (int i = 0; i < nl; ++i) {
+        const psalm_pr_layer* ly = &d->layers[i];
+        const int l = i % nlev, j = i / nlev, h = hw_levels_host[2 * l], w = hw_levels_host[2 * l + 1], hw = h * w, N = nl_l[l] * D;
+        PR(psalm_attn_mask(masks, amask, flags, R, H2, W2, h, w, stream));
+        if (!fuse) PR(g32(outq, D, ly->cq_w, ly->cq_b, nullptr, qp, D, 0));
+        PR(psalm_mha_attention_f32_shared(qp, D, Kl[l] + (long)j * D, N, Vl[l] + (long)j * D, N, a, D, amask, flags, mha, B, Q, hw, nh, 32, stream));
+        PR(g32(a, D, ly->co_w, ly->co_b, out, x1, D, 0));
+        float* o1 = outb[cur];
+        if (fuse) {
+            PR(psalm_layernorm_chain(x1, D, o1, D, ly->cn_g, ly->cn_b, d->query_embed, Q, outq, D, nullptr, nullptr, nullptr, 0, R, D, eps, stream));
+            PR(psalm_gemm_f32_rows_pair(outq, ly->sqk_w, ly->sqk_b, qk, R, 2 * D, D, 0, o1, ly->sv_w, ly->sv_b, v, R, D, D, 0, stream));
+        } else {
+            PR(ln(x1, ly->cn_g, ly->cn_b, o1));
+            PR(psalm_add_bcast(o1, PSALM_F32, d->query_embed, PSALM_F32, outq, PSALM_F32, R, D, Q, stream));
+            PR(g32(outq, D, ly->sqk_w, ly->sqk_b, nullptr, qk, 2 * D, 0));
+            PR(g32(o1, D, ly->sv_w, ly->sv_b, nullptr, v, D, 0));
+        }
+        PR(psalm_mha_attention_f32(qk, 2L * D, qk + D, 2L * D, v, D, a, D, nullptr, nullptr, mha, B, Q, Q, nh, 32, stream));
+        PR(g32(a, D, ly->so_w, ly->so_b, o1, x1, D, 0));
+        float* o2 = outb[cur ^ 1];
+        PR(ln(x1, ly->sn_g, ly->sn_b, o2));
+        PR(g32(o2, D, ly->f1_w, ly->f1_b, nullptr, hdd, F, 1));
+        PR(g32(hdd, F, ly->f2_w, ly->f2_b, o2, x1, D, 0));
+        if (fuse) {
+            PR(psalm_layernorm_chain(x1, D, o1, D, ly->fn_g, ly->fn_b, d->query_embed, Q, outq, D, d->dn_g, d->dn_b, dec, D, R, D, eps, stream));
+        } else {
+            PR(ln(x1, ly->fn_g, ly->fn_b, o1));
+            PR(psalm_add_bcast(o1, PSALM_F32, d->query_embed, PSALM_F32, outq, PSALM_F32, R, D, Q, stream));
+        }
+        out = o1;
+        PR(mask_head(out, fuse, i + 1 < nl ? &d->layers[i + 1] : nullptr, i + 1 < nl ? masks : pred_masks));
+        cur ^= 1;
+    }
+    // ---- prediction heads of the last layer: the two MLP layers over all B * Q rows, then ONE grouped launch per head for the prompts' ragged products
+    struct Head { const float* w0; const float* b0; const float* w1; const float* b1; const HeadIn* in; float* h0; float* h1; };
+    Head hd[3];
+    int nh_ = 0;
+    const float* const* W0s[3] = {d->CLASS_w, d->SEG_w, d->REGION_w};
+    const float* const* B0s[3] = {d->CLASS_b, d->SEG_b, d->REGION_b};
+    for (int k = 0; k < 3; ++k)
+        if (hin[k].emb && hin[k].off && hin[k].off[B] > 0) hd[nh_++] = Head{W0s[k][0], B0s[k][0], W0s[k][1], B0s[k][1], &hin[k], nullptr, nullptr};
+    auto emb = [&](const Head& x) -> int {
+        const float* As[16]; const float* Ws[16]; float* Cs[16]; int Ms[16], Ns[16];
+        for (int b = 0; b < B; ++b) {
+            const int o0 = x.in->off[b], n = x.in->off[b + 1] - o0;
+            const float* e = x.in->emb + (long)o0 * D; const float* hq = x.h1 + (long)b * Q * D;
+            float* c = x.in->out + (long)o0 * Q;                  // (Q, n) after the o0 columns of the prompts before / (n, Q) after their o0 rows
+            if (x.in->rows_are_emb) { As[b] = e; Ws[b] = hq; Ms[b] = n; Ns[b] = Q; }
+            else { As[b] = hq; Ws[b] = e; Ms[b] = Q; Ns[b] = n; }
+            Cs[b] = c;
+        }
+        return psalm_gemm_f32_grouped(As, Ws, Cs, Ms, Ns, D, B, stream);
+    };
+    int first = 0;
+    if (fuse && nh_ >= 2) {
+        Head& x = hd[0]; Head& y = hd[1];
+        x.h0 = t0; x.h1 = t1; y.h0 = me0; y.h1 = me1;
+        PR(psalm_gemm_f32_rows_pair(dec, x.w0, x.b0, x.h0, R, D, D, 1, dec, y.w0, y.b0, y.h0, R, D, D, 1, stream));
+        PR(psalm_gemm_f32_rows_pair(x.h0, x.w1, x.b1, x.h1, R, D, D, 0, y.h0, y.w1, y.b1, y.h1, R, D, D, 0, stream));
+        PR(emb(x)); PR(emb(y));
+        first = 2;
+    }
+    for (int i = first; i < nh_; ++i) {
+        Head& x = hd[i];
+        x.h0 = t0; x.h1 = t1;
+        PR(g32(dec, D, x.w0, x.b0, nullptr, x.h0, D, 1));
+        PR(g32(x.h0, D, x.w1, x.b1, nullptr, x.h1, D, 0));
+        PR(emb(x));
+    }
+#undef PR
+    return 0;
+}
+
 
 // ------------------------------------------------------------------------------------------------------------------ post-processing
 // psalm_postprocess: llava_phi.py:1401-1466 for one image (see psalm_hip.h), the launch sequence of PSALM._post_head + PSALM._post_tail.

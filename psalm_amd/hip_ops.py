@@ -49,7 +49,7 @@ def _dt(t: torch.Tensor) -> int:
         raise PsalmHipError(f"unsupported dtype {t.dtype} (float32 / bfloat16 only)")
 
 
-ABI_VERSION = 10       # == PSALM_ABI_VERSION of include/psalm_hip.h (tests/test_0_abi.py compares the two and the built library's answer)
+ABI_VERSION = 11       # == PSALM_ABI_VERSION of include/psalm_hip.h (tests/test_0_abi.py compares the two and the built library's answer)
 
 
 class _ProfiledLib:
@@ -707,6 +707,73 @@ class Ops:
         self._check(rc, "psalm_predictor_forward")
         return masks, cls, seg, reg
 
+    def predictor_kv_bytes(self, desc, shapes, mf_size):
+        """bytes of the front psalm_predictor_kv writes (and psalm_predictor_forward_batched reads) at the start of its workspace"""
+        hw = (c_int * (2 * len(shapes)))(*[int(v) for s_ in shapes for v in s_])
+        self.lib.psalm_predictor_kv_bytes.restype = c_long
+        n = self.lib.psalm_predictor_kv_bytes(ctypes.byref(desc), hw, int(mf_size[0]), int(mf_size[1]))
+        if n < 0:
+            raise PsalmHipError(f"psalm_predictor_kv_bytes: {self.lib.psalm_last_error().decode()}")
+        return int(n)
+
+    def predictor_forward_batched(self, desc, shapes, kv, mf, mf_size, seg_query, class_emb=None, cls_counts=None, seg_emb=None, seg_counts=None,
+                                  region_emb=None, reg_counts=None, offsets=None):
+        """The masked-attention decoder for B prompts of ONE image as ONE native call over B * Q query rows (psalm_predictor_forward_batched).
+        kv: `predictor_kv`'s handle (only read; any region count); seg_query (B*Q, D); *_emb: the prompts' embeddings packed in prompt order, *_counts
+        their per-prompt row counts (or offsets = {"cls" | "seg" | "region": (B + 1) offsets} given verbatim).  Returns (pred_masks (B*Q, H2*W2),
+        cls_logits, seg_logits, region_logits): the logits packed -- prompt b's (Q, n_b) block (region: (n_b, Q)) behind those of the prompts before
+        it, flat float32 -- or None.  The scratch is a per-stage workspace of the binding."""
+        H2, W2 = mf_size
+        Q, D = desc.Q, desc.D
+        if seg_query.dim() != 2 or seg_query.shape[0] % Q:
+            raise PsalmHipError("predictor_forward_batched: seg_query (B*Q, D)")
+        B = int(seg_query.shape[0]) // Q
+        for t in [mf, seg_query] + [e for e in (class_emb, seg_emb, region_emb) if e is not None]:
+            if t.dtype != torch.float32 or not t.is_contiguous() or t.data_ptr() % 16:
+                raise PsalmHipError("predictor_forward_batched: contiguous, 16-byte aligned float32 tensors")
+        offsets = offsets or {}
+
+        def offs(name, emb, counts):
+            if emb is None:
+                return None, 0
+            o_ = offsets.get(name)
+            if o_ is None:
+                if counts is None or len(counts) != B:
+                    raise PsalmHipError(f"predictor_forward_batched: one {name} count per prompt")
+                o_ = [0]
+                for c in counts:
+                    o_.append(o_[-1] + int(c))
+                if o_[-1] != emb.shape[0]:
+                    raise PsalmHipError(f"predictor_forward_batched: the {name} counts do not add up to the embedding rows")
+            o_ = [int(v) for v in o_]
+            if len(o_) != B + 1 or o_[-1] > emb.shape[0]:
+                raise PsalmHipError(f"predictor_forward_batched: (B + 1) {name} offsets within the embedding rows")
+            return (c_int * (B + 1))(*o_), max(o_[-1], 0)
+
+        c_off, n_c = offs("cls", class_emb, cls_counts)
+        s_off, n_s = offs("seg", seg_emb, seg_counts)
+        r_off, n_r = offs("region", region_emb, reg_counts)
+        hw = (c_int * (2 * len(shapes)))(*[int(v) for s_ in shapes for v in s_])
+        self.lib.psalm_predictor_forward_batched_workspace.restype = c_long
+        nbytes = self.lib.psalm_predictor_forward_batched_workspace(ctypes.byref(desc), hw, H2, W2, B, n_r)
+        if nbytes < 0:
+            raise PsalmHipError(f"psalm_predictor_forward_batched_workspace: {self.lib.psalm_last_error().decode()}")
+        kws, koff, kbytes, _ = kv
+        if kbytes < self.predictor_kv_bytes(desc, shapes, mf_size):
+            raise PsalmHipError("predictor_forward_batched: the K / V workspace was prepared for another geometry")
+        ws = self._stage_ws("predictor_batched", nbytes + 256)
+        off = (-ws.data_ptr()) % 256
+        masks = self.empty(B * Q, H2 * W2, dtype=torch.float32)
+        cls = self.empty(Q * n_c, dtype=torch.float32) if class_emb is not None else None
+        seg = self.empty(Q * n_s, dtype=torch.float32) if seg_emb is not None else None
+        reg = self.empty(n_r * Q, dtype=torch.float32) if region_emb is not None else None
+        rc = self.lib.psalm_predictor_forward_batched(ctypes.byref(desc), hw, c_void_p(kws.data_ptr() + koff), self._p(mf), H2, W2, B, self._p(seg_query),
+                                                      self._p(class_emb), c_off, self._p(seg_emb), s_off, self._p(region_emb), r_off, self._p(masks),
+                                                      self._p(cls), self._p(seg), self._p(reg), c_void_p(ws.data_ptr() + off), c_long(nbytes),
+                                                      self._p(self._gemm_ws()), c_long(self.GEMM_WS_BYTES), self._stream())
+        self._check(rc, "psalm_predictor_forward_batched")
+        return masks, cls, seg, reg
+
     POST_TASKS = {"semantic": 0, "instance": 1, "panoptic": 2, "referring": 3, "region": 4}
 
     def postprocess(self, task, sizes, pred_masks=None, mask_up=None, cls_logits=None, seg_logits=None, region_logits=None, is_thing=None,
@@ -1023,6 +1090,43 @@ class Ops:
         self._check(rc, "psalm_gemm_f32_pair")
         return c0, c1
 
+    def gemm_f32_rows(self, a, w, bias=None, residual=None, act=ACT_NONE):
+        """act(a . w^T + bias) + residual on the exact-fp32 skinny kernel over cdiv(M, 32) row tiles (psalm_gemm_f32_rows; M <= 2048, N <= 8192):
+        row r carries the words gemm() returns for any <= 192-row set holding it.  a / residual may be row-strided float32 views."""
+        M, K = a.shape
+        N = w.shape[0]
+        out = self.empty(M, N, dtype=torch.float32)
+        rc = self.lib.psalm_gemm_f32_rows(self._pv(a), c_long(a.stride(0)), self._pv(w), c_long(w.stride(0)), self._pv(bias), self._pv(residual),
+                                          c_long(residual.stride(0) if residual is not None else 0), self._p(out), c_long(N), M, N, K, act, self._stream())
+        self._check(rc, "psalm_gemm_f32_rows")
+        return out
+
+    def gemm_f32_rows_pair(self, a0, w0, bias0, a1, w1, bias1, act0=ACT_NONE, act1=ACT_NONE):
+        """gemm_f32_pair with M <= 2048 (psalm_gemm_f32_rows_pair)"""
+        c0 = self.empty(a0.shape[0], w0.shape[0], dtype=torch.float32)
+        c1 = self.empty(a1.shape[0], w1.shape[0], dtype=torch.float32)
+        rc = self.lib.psalm_gemm_f32_rows_pair(self._p(a0), self._p(w0), self._pv(bias0), self._p(c0), a0.shape[0], w0.shape[0], a0.shape[1], act0,
+                                               self._p(a1), self._p(w1), self._pv(bias1), self._p(c1), a1.shape[0], w1.shape[0], a1.shape[1], act1, self._stream())
+        self._check(rc, "psalm_gemm_f32_rows_pair")
+        return c0, c1
+
+    def gemm_f32_grouped(self, a_list, w_list):
+        """[a_i . w_i^T] for <= 16 (a_i (M_i, K), w_i (N_i, K)) contiguous float32 pairs of one K in ONE launch (psalm_gemm_f32_grouped; M_i <= 192)"""
+        n = len(a_list)
+        if n != len(w_list) or not 1 <= n <= 16:
+            raise PsalmHipError("gemm_f32_grouped: 1..16 problems")
+        K = int(a_list[0].shape[1])
+        for a, w in zip(a_list, w_list):
+            if a.dtype != torch.float32 or w.dtype != torch.float32 or a.dim() != 2 or w.dim() != 2 or a.shape[1] != K or w.shape[1] != K:
+                raise PsalmHipError("gemm_f32_grouped: float32 (M_i, K) x (N_i, K) operands of one K")
+        outs = [self.empty(a.shape[0], w.shape[0], dtype=torch.float32) for a, w in zip(a_list, w_list)]
+        VP, VI = c_void_p * n, c_int * n
+        rc = self.lib.psalm_gemm_f32_grouped(VP(*[self._p(a).value or 0 for a in a_list]), VP(*[self._p(w).value or 0 for w in w_list]),
+                                             VP(*[self._p(c).value or 0 for c in outs]), VI(*[int(a.shape[0]) for a in a_list]),
+                                             VI(*[int(w.shape[0]) for w in w_list]), K, n, self._stream())
+        self._check(rc, "psalm_gemm_f32_grouped")
+        return outs
+
     def add_bcast(self, a, b, out_dtype=None):
         """out[r] = a[r] + b[r % b_rows]   (a (rows,C), b (b_rows,C))."""
         rows, C = a.shape
@@ -1268,15 +1372,20 @@ class Ops:
         self._check(rc, "psalm_causal_attention_f32_prefix_grouped_split")
         return split_out
 
-    def mha_attention(self, q, k, v, B, Lq, Lk, heads, mask=None, row_all_masked=None):
-        """q (B*Lq, D) / k, v (B*Lk, D) row-strided views, head_dim 32; mask (B,Lq,Lk) u8 1 = blocked."""
+    def mha_attention(self, q, k, v, B, Lq, Lk, heads, mask=None, row_all_masked=None, workspace=None):
+        """q (B*Lq, D) / k, v (B*Lk, D) row-strided views, head_dim 32; mask (B,Lq,Lk) u8 1 = blocked.  workspace: a caller's uint8 buffer for the
+        fp32 kernel's partial states (psalm_mha_attention_f32_workspace bytes) instead of the binding's cached one."""
         D = heads * 32
         out = self.empty(B * Lq, D, dtype=q.dtype)
         if q.dtype == torch.float32 and Lq <= 128 and all(t.stride(0) % 4 == 0 and t.data_ptr() % 16 == 0 for t in (q, k, v)):
             self.lib.psalm_mha_attention_f32_workspace.restype = c_long          # fp32 matrix-core kernel, split over 256-key chunks
             nbytes = self.lib.psalm_mha_attention_f32_workspace(B, heads, Lq, Lk)
             ws = None
-            if nbytes:
+            if nbytes and workspace is not None:
+                if workspace.dtype != torch.uint8 or workspace.numel() < nbytes:
+                    raise PsalmHipError(f"mha_attention: workspace of >= {nbytes} bytes (uint8)")
+                ws = workspace
+            elif nbytes:
                 key = ("mha_f32_ws", nbytes)
                 ws = self._ws.get(key)
                 if ws is None:
@@ -1290,6 +1399,31 @@ class Ops:
                                           c_long(v.stride(0)), self._p(out), c_long(D), _dt(q), self._p(mask),
                                           self._p(row_all_masked), B, Lq, Lk, heads, 32, self._stream())
         self._check(rc, "psalm_mha_attention")
+        return out
+
+    def mha_attention_f32_shared_workspace(self, B, heads, Lq, Lk):
+        self.lib.psalm_mha_attention_f32_shared_workspace.restype = c_long
+        return int(self.lib.psalm_mha_attention_f32_shared_workspace(B, heads, Lq, Lk))
+
+    def mha_attention_f32_shared(self, q, k, v, B, Lq, Lk, heads, mask=None, row_all_masked=None, workspace=None):
+        """B query sets against ONE K / V (psalm_mha_attention_f32_shared): q (B*Lq, D), k / v (Lk, D) row-strided float32 views, mask (B, Lq, Lk) u8
+        1 = blocked, row_all_masked (B*Lq) u8.  Set b's words are those of mha_attention(B = 1) on it alone.  workspace: as mha_attention's."""
+        D = heads * 32
+        if q.dtype != torch.float32 or k.dtype != torch.float32 or v.dtype != torch.float32 or q.shape[0] != B * Lq or k.shape[0] != Lk or v.shape[0] != Lk:
+            raise PsalmHipError("mha_attention_f32_shared: float32 q (B*Lq, D), k / v (Lk, D)")
+        out = self.empty(B * Lq, D, dtype=torch.float32)
+        nbytes = self.mha_attention_f32_shared_workspace(B, heads, Lq, Lk)
+        ws = None
+        if nbytes and workspace is not None:
+            if workspace.dtype != torch.uint8 or workspace.numel() < nbytes:
+                raise PsalmHipError(f"mha_attention_f32_shared: workspace of >= {nbytes} bytes (uint8)")
+            ws = workspace
+        elif nbytes:
+            ws = self._stage_ws("mha_f32_shared", nbytes)
+        rc = self.lib.psalm_mha_attention_f32_shared(self._pv(q), c_long(q.stride(0)), self._pv(k), c_long(k.stride(0)), self._pv(v),
+                                                     c_long(v.stride(0)), self._p(out), c_long(D), self._p(mask), self._p(row_all_masked),
+                                                     self._p(ws), B, Lq, Lk, heads, 32, self._stream())
+        self._check(rc, "psalm_mha_attention_f32_shared")
         return out
 
     def mha_attention_t(self, q, k, vt, B, Lq, Lk, heads, mask=None, row_all_masked=None):

@@ -1625,6 +1625,93 @@ class PSALM:
             oh, ow = int(rows[-1] - rows[0] + 1), int(cols[-1] - cols[0] + 1)
         return (Hpad, Wpad, oh, ow, int(info.get("height", Hi)), int(info.get("width", Wi)))
 
+    # The mask decoder over the prompts of a session: one native pass over B * Q query rows against the session's one K / V front
+    # (psalm_predictor_forward_batched) in place of B `predictor` calls.  Each prompt's words are those of its own call, so the switch changes time only.
+    batch_decoder = True
+    decoder_batch_max = 8            # prompts per pass: scratch + outputs hold ~2 * B * Q * H2*W2 * 4 bytes of mask logits (1024^2: ~52 MB per prompt)
+
+    def _decode_batched(self, session, prompts):
+        """`predictor`'s result dicts for the prompts of ONE session -- prompts: a list of (seg_query (Q, D), SEG_emb, class_emb, region_emb) as the
+        per-prompt loop passes them -- through the batched decoder, in chunks of `decoder_batch_max`; None when the per-prompt loop must run: fewer
+        than two prompts, `batch_decoder` off, or a prompt outside the native per-prompt path's conditions."""
+        o, cfg = self.ops, self.cfg
+        n = len(prompts)
+        step = int(self.decoder_batch_max)
+        if n < 2 or not self.batch_decoder or step < 2:
+            return None
+        mf, shapes, mfs = session.mask_features, session.shapes, session.mask_features_size
+        if not self._predictor_native_ok(mf):
+            return None
+        Q, D = cfg.md_queries, cfg.md_hidden
+        for sq, se, ce, re in prompts:
+            if sq.dtype != torch.float32 or sq.data_ptr() % 16 or not sq.is_contiguous():
+                return None
+            if any(e is not None and (e.dtype != torch.float32 or e.data_ptr() % 16 or not e.is_contiguous()) for e in (se, ce, re)):
+                return None
+            if (re is not None and re.shape[0] > 192) or any(e is not None and e.shape[0] > 8192 for e in (se, ce)):
+                return None                                       # (outside the exact-fp32 skinny kernel's range: the per-prompt call takes another kernel)
+        kinds = [tuple(e is not None for e in p[1:]) for p in prompts]
+        if len(set(kinds)) != 1:
+            return None
+        kv = self._session_kv(session, int(prompts[0][3].shape[0]) if prompts[0][3] is not None else 0)
+        if kv is None:
+            return None
+        handle, _, mf_c = kv
+        desc, _ = self._predictor_desc(shapes)
+        H2, W2 = mfs
+
+        def rows(pieces):                                         # consecutive slices of one tensor stay a view; others are packed by stream copies
+            if all(a.data_ptr() + a.numel() * 4 == b_.data_ptr() and a.untyped_storage().data_ptr() == b_.untyped_storage().data_ptr()
+                   for a, b_ in zip(pieces, pieces[1:])):
+                return pieces[0].as_strided((sum(int(t.shape[0]) for t in pieces), D), (D, 1))
+            out = o.empty(sum(int(t.shape[0]) for t in pieces), D)
+            r0 = 0
+            for t in pieces:
+                if t.shape[0]:
+                    o.copy_(out[r0:r0 + t.shape[0]], t)
+                r0 += int(t.shape[0])
+            return out
+
+        def own(t):                                               # a prompt's block of the packed logits, 16-byte aligned as a per-prompt call's tensor is
+            if t.data_ptr() % 16 == 0:
+                return t
+            return o.copy_(o.empty(*t.shape), t)
+
+        outs = []
+        for c0 in range(0, n, step):
+            chunk = prompts[c0:c0 + step]
+            B = len(chunk)
+            if B == 1:                                            # (a trailing chunk of one prompt: the per-prompt call, the same words)
+                sq, se, ce, re = chunk[0]
+                outs.append(self.predictor(session.multi_scale_features, shapes, mf, mfs, sq, se, ce, re,
+                                           kv=self._session_kv(session, int(re.shape[0]) if re is not None else 0)))
+                continue
+            has_s, has_c, has_r = kinds[0]
+            cnt = lambda k: [int(p[k].shape[0]) for p in chunk]  # noqa: E731
+            masks, cls_l, seg_l, reg_l = o.predictor_forward_batched(
+                desc, shapes, handle, mf_c, mfs, rows([p[0] for p in chunk]),
+                class_emb=rows([p[2] for p in chunk]) if has_c else None, cls_counts=cnt(2) if has_c else None,
+                seg_emb=rows([p[1] for p in chunk]) if has_s else None, seg_counts=cnt(1) if has_s else None,
+                region_emb=rows([p[3] for p in chunk]) if has_r else None, reg_counts=cnt(3) if has_r else None)
+            oc = os_ = or_ = 0
+            for b, (sq, se, ce, re) in enumerate(chunk):
+                r = {"pred_masks": masks[b * Q:(b + 1) * Q].view(Q, H2, W2), "pred_class_name_logits": None, "pred_SEG_logits": None,
+                     "pred_region_logits": None}
+                if has_c:
+                    k = int(ce.shape[0])
+                    r["pred_class_name_logits"] = own(cls_l[Q * oc:Q * (oc + k)].view(Q, k))
+                    oc += k
+                if has_s:
+                    k = int(se.shape[0])
+                    r["pred_SEG_logits"] = own(seg_l[Q * os_:Q * (os_ + k)].view(Q, k))
+                    os_ += k
+                if has_r:
+                    k = int(re.shape[0])
+                    r["pred_region_logits"] = own(reg_l[Q * or_:Q * (or_ + k)].view(k, Q))
+                    or_ += k
+                outs.append(r)
+        return outs
+
     @torch.no_grad()
     def segment(self, session: "ImageSession", input_ids, attention_mask=None, *, seg_info=None, class_name_ids=None,
                 class_name_embedding_indices=None, cls_indices=None, token_refer_id=None, refer_embedding_indices=None, is_thing_list=None,
@@ -1700,6 +1787,7 @@ class PSALM:
         Hi, Wi = int(session.images.shape[2]), int(session.images.shape[3])
         outs = []
         c0 = r0 = 0
+        prompts = []
         for b in range(N):
             nc = sp["n_cls"][b]
             ce = cls_emb[c0:c0 + nc] if cls_emb is not None else None
@@ -1709,7 +1797,12 @@ class PSALM:
             if reg_emb is not None:
                 re = reg_emb[r0:r0 + n_regions[b]]
                 r0 += n_regions[b]
-            r = self.predictor(ms, shapes, mf, mfs, seg_q[b * Q:(b + 1) * Q], se, ce, re, kv=self._session_kv(session, n_regions[b] if n_regions else 0))
+            prompts.append((seg_q[b * Q:(b + 1) * Q], se, ce, re))
+        decoded = self._decode_batched(session, prompts)         # (None: the per-prompt loop below)
+        for b in range(N):
+            sq, se, ce, re = prompts[b]
+            r = decoded[b] if decoded is not None else self.predictor(ms, shapes, mf, mfs, sq, se, ce, re,
+                                                                      kv=self._session_kv(session, n_regions[b] if n_regions else 0))
             if not postprocess:
                 outs.append(r)
                 continue
@@ -1850,10 +1943,10 @@ class PSALM:
                              w["region_projector.b"], out_dtype=self.adt)
         results = []
         g = c0 = r0 = 0
+        # every prompt's decoder operands, then the prompts of all requests naming one session as one batch of the decoder (different sessions have
+        # different K / V: separate calls)
+        prompts, by_session = [], {}
         for session, sp, N, seg_info, n_regions in plans:
-            mf, ms, shapes, mfs = session.mask_features, session.multi_scale_features, session.shapes, session.mask_features_size
-            Hi, Wi = int(session.images.shape[2]), int(session.images.shape[3])
-            outs = []
             for b in range(N):
                 nc = sp["n_cls"][b]
                 ce = cls_emb[c0:c0 + nc] if cls_emb is not None else None
@@ -1863,8 +1956,23 @@ class PSALM:
                 if reg_emb is not None:
                     re = reg_emb[r0:r0 + n_regions[b]]
                     r0 += n_regions[b]
-                res = self.predictor(ms, shapes, mf, mfs, seg_q[g * Q:(g + 1) * Q], se, ce, re,
-                                     kv=self._session_kv(session, n_regions[b] if n_regions else 0))
+                prompts.append((seg_q[g * Q:(g + 1) * Q], se, ce, re))
+                by_session.setdefault(id(session), (session, []))[1].append(g)
+                g += 1
+        decoded = {}
+        for session, gs in by_session.values():
+            rs = self._decode_batched(session, [prompts[i] for i in gs])
+            if rs is not None:
+                decoded.update(zip(gs, rs))
+        g = 0
+        for session, sp, N, seg_info, n_regions in plans:
+            mf, ms, shapes, mfs = session.mask_features, session.multi_scale_features, session.shapes, session.mask_features_size
+            Hi, Wi = int(session.images.shape[2]), int(session.images.shape[3])
+            outs = []
+            for b in range(N):
+                sq, se, ce, re = prompts[g]
+                res = decoded[g] if g in decoded else self.predictor(ms, shapes, mf, mfs, sq, se, ce, re,
+                                                                     kv=self._session_kv(session, n_regions[b] if n_regions else 0))
                 g += 1
                 if postprocess:
                     res = self._finalize(self._postprocess(res, self._post_sizes(Hi, Wi, seg_info[b], cfg.size_divisibility)), seg_info[b])
