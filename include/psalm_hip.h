@@ -37,8 +37,9 @@ const char* psalm_last_error(void);
  * 10: grouped image sessions: psalm_prefix_ref, psalm_causal_attention_f32_prefix_grouped[_split] (+ _workspace), the stage-level
  *    psalm_phi_suffix_grouped (+ _workspace).
  * 11: the mask decoder over all prompts of an image session: psalm_mha_attention_f32_shared (+ _workspace), psalm_gemm_f32_rows[_pair],
- *    psalm_gemm_f32_grouped, psalm_predictor_kv_bytes, the stage-level psalm_predictor_forward_batched (+ _workspace). */
-#define PSALM_ABI_VERSION 11
+ *    psalm_gemm_f32_grouped, psalm_predictor_kv_bytes, the stage-level psalm_predictor_forward_batched (+ _workspace).
+ * 12: region prompts of image sessions: psalm_mask_rasterize, psalm_mask_dilate_disc, psalm_region_best, psalm_mask_gather_u8. */
+#define PSALM_ABI_VERSION 12
 int psalm_abi_version(void);
 const char* psalm_backend(void); /* "hip-gfx950" */
 
@@ -743,6 +744,27 @@ int psalm_mask_resize_nearest_pad(const unsigned char* in, int R, int h, int w, 
  * (masks[r].nonzero() / [Sh, Sw])[idx[r][i]].float(), bit for bit (correctly rounded fp32 division).  masks (R,Sh,Sw) u8, row_cnt (R,Sh) i32 as
  * psalm_mask_resize_nearest_pad leaves it, idx (R,n) i32, pts (R,n,2) f32; a rank outside [0, non-zero pixels) gives (0, 0).  Sh <= 8192. */
 int psalm_mask_select_points(const unsigned char* masks, const int* row_cnt, const int* idx, int R, int Sh, int Sw, int n, float* pts, void* stream);
+
+/* ------------------------------------------------------------------------------------------------------------------
+ * Region prompts of image sessions (csrc/prompts.hip; PSALM.segment(..., regions=...)): the dataset mapper's host preparation of a click / box /
+ * scribble prompt (coco_instance_mapper.py:233-252) on the device, in front of psalm_mask_resize_nearest_pad / psalm_mask_select_points.  Integer
+ * results, exact against the host formulas; nothing allocates or synchronises. */
+typedef struct { int region, kind, a, b, c, d; } psalm_prompt_prim;   /* kind 0: pixel (y = a, x = b); kind 1: box rows [a, c) x cols [b, d) */
+/* masks (R,h,w) u8 = 0 (a memset node on `stream`, issued by the call), then 1 at every pixel of every primitive of region prims[i].region (box
+ * convention of bulid_COCO_Interactivate.py:72, [min_row:max_row, min_col:max_col] = 1).  prims_dev: n_prims records on the device.  A primitive, or the
+ * part of one, outside the image or with `region` outside [0, R) writes nothing; kinds other than 0 / 1 are ignored.  n_prims == 0 leaves zeros, R == 0
+ * is a no-op. */
+int psalm_mask_rasterize(const psalm_prompt_prim* prims_dev, int n_prims, int R, int h, int w, unsigned char* masks, void* stream);
+/* enhance_with_circles (coco_instance_mapper.py:17-33) per plane: out[r] = union of the integer discs dy^2 + dx^2 <= radius[r]^2 around every pixel of
+ * in[r] that EQUALS 1 (0 / 1 bytes out); radius[r] < 0 copies plane r unchanged.  radius_dev (R) i32 on the device, every entry <= max_radius (larger
+ * ones are clamped), 0 <= max_radius <= 16; in != out; h * w < 2^31, R <= 65535. */
+int psalm_mask_dilate_disc(const unsigned char* in, const int* radius_dev, int max_radius, int R, int h, int w, unsigned char* out, void* stream);
+/* scores (Q,R) f32 (NaN-free) -> best_query[r] = arg-max over q of scores[q][r], the LOWEST q among equal maxima (psalm_video_pick's tie rule;
+ * torch.topk(.., 1) of region_segmentation.py:163 leaves ties open), best_score[r] = that score.  1 <= Q <= 1024, R >= 1. */
+int psalm_region_best(const float* scores, int Q, int R, int* best_query, float* best_score, void* stream);
+/* out (R,HW) u8: out[r][p] = masks[query[r]][p] > 0 (psalm_binarize_gather's test, one byte per pixel); masks (Q,HW) f32, query (R) i32 on the device,
+ * an entry outside [0, Q) gives an empty mask. */
+int psalm_mask_gather_u8(const float* masks, const int* query, int Q, int R, long HW, unsigned char* out, void* stream);
 
 #ifdef __cplusplus
 }

@@ -49,7 +49,7 @@ def _dt(t: torch.Tensor) -> int:
         raise PsalmHipError(f"unsupported dtype {t.dtype} (float32 / bfloat16 only)")
 
 
-ABI_VERSION = 11       # == PSALM_ABI_VERSION of include/psalm_hip.h (tests/test_0_abi.py compares the two and the built library's answer)
+ABI_VERSION = 12       # == PSALM_ABI_VERSION of include/psalm_hip.h (tests/test_0_abi.py compares the two and the built library's answer)
 
 
 class _ProfiledLib:
@@ -1780,6 +1780,52 @@ class Ops:
         rc = self.lib.psalm_mask_select_points(self._p(masks), self._p(row_cnt), self._p(idx), R, Sh, Sw, n, self._p(pts), self._stream())
         self._check(rc, "psalm_mask_select_points")
         return pts
+
+    # ------------------------------------------------------------------ region prompts of image sessions (csrc/prompts.hip)
+    def mask_rasterize(self, prims, R, h, w, out=None):
+        """prims (n,6) i32 rows of psalm_prompt_prim (region, kind, a, b, c, d; kind 0: pixel (a, b), kind 1: box rows [a,c) x cols [b,d)) on the
+        device -> masks (R,h,w) u8, zeroed by the call: psalm_mask_rasterize."""
+        n = int(prims.shape[0])
+        self._want(prims, torch.int32, (n, 6), "mask_rasterize prims")
+        out = self.empty(R, h, w, dtype=torch.uint8) if out is None else self._want(out, torch.uint8, (R, h, w), "mask_rasterize out")
+        rc = self.lib.psalm_mask_rasterize(self._p(prims) if n else c_void_p(0), n, int(R), int(h), int(w), self._p(out), self._stream())
+        self._check(rc, "psalm_mask_rasterize")
+        return out
+
+    def mask_dilate_disc(self, masks, radius, max_radius, out=None):
+        """masks (R,h,w) u8, radius (R) i32 on the device (< 0: the plane is copied), 0 <= max_radius <= 16 bounding every radius -> (R,h,w) u8,
+        enhance_with_circles per plane: psalm_mask_dilate_disc.  `out` must not be `masks`."""
+        if masks.dim() != 3 or masks.dtype != torch.uint8:
+            raise PsalmHipError("mask_dilate_disc: masks (R,h,w) uint8")
+        R, h, w = masks.shape
+        self._want(radius, torch.int32, (R,), "mask_dilate_disc radius")
+        out = self.empty(R, h, w, dtype=torch.uint8) if out is None else self._want(out, torch.uint8, (R, h, w), "mask_dilate_disc out")
+        rc = self.lib.psalm_mask_dilate_disc(self._p(masks), self._p(radius), int(max_radius), R, h, w, self._p(out), self._stream())
+        self._check(rc, "psalm_mask_dilate_disc")
+        return out
+
+    def region_best(self, scores, best_query=None, best_score=None):
+        """scores (Q,R) f32 -> (best_query (R) i32: first arg-max of column r, best_score (R) f32): psalm_region_best.  The outputs may be given
+        (views of a caller-owned block)."""
+        if scores.dim() != 2 or scores.dtype != torch.float32:
+            raise PsalmHipError("region_best: scores (Q,R) float32")
+        Q, R = scores.shape
+        best_query = self.empty(R, dtype=torch.int32) if best_query is None else self._want(best_query, torch.int32, (R,), "region_best best_query")
+        best_score = self.empty(R, dtype=torch.float32) if best_score is None else self._want(best_score, torch.float32, (R,), "region_best best_score")
+        self._check(self.lib.psalm_region_best(self._p(scores), Q, R, self._p(best_query), self._p(best_score), self._stream()), "psalm_region_best")
+        return best_query, best_score
+
+    def mask_gather_u8(self, masks, query):
+        """masks (Q,H,W) f32, query (R) i32 -> (R,H,W) u8 = masks[query] > 0: psalm_mask_gather_u8."""
+        if masks.dim() != 3 or masks.dtype != torch.float32:
+            raise PsalmHipError("mask_gather_u8: masks (Q,H,W) float32")
+        Q, Hh, Ww = masks.shape
+        R = int(query.numel())
+        self._want(query, torch.int32, (R,), "mask_gather_u8 query")
+        out = self.empty(R, Hh, Ww, dtype=torch.uint8)
+        rc = self.lib.psalm_mask_gather_u8(self._p(masks), self._p(query), Q, R, c_long(Hh * Ww), self._p(out), self._stream())
+        self._check(rc, "psalm_mask_gather_u8")
+        return out
 
 
 _OPS: Optional[Ops] = None

@@ -97,6 +97,17 @@ def default_region_point_sampler(nonzero: torch.Tensor, n: int) -> torch.Tensor:
     return torch.randperm(m)[:n]
 
 
+def default_region_index_sampler(m: int, n: int) -> torch.Tensor:
+    """`default_region_point_sampler` (context_cluster.py:31-40 rand_sample_repeat) with the number of non-zero pixels as its argument: row indices
+    into a `nonzero()` of m rows.  The same global-RNG calls in the same order."""
+    m = int(m)
+    if m < n:
+        return torch.cat((torch.arange(m), torch.randint(0, m, (n - m,))))
+    if m == n:
+        return torch.arange(m)
+    return torch.randperm(m)[:n]
+
+
 class _VisionTower:
     """What `model.get_vision_tower()` hands the reference's builder (psalm/model/builder.py:57-65): `.image_processor` -- the dict
     of the three dataset mappers (llava_phi.py:66-69) -- and a `.to(...)` that the builder calls to move the tower."""
@@ -126,6 +137,7 @@ class ImageSession:
         self.prefix_len = 0                       # P
         self.prefix_cache = None                  # (buffer, per-layer (K (heads, ceil32 P, 64), V (P, hidden)) views)
         self.prefix_builds = self.prefix_hits = 0
+        self.region_tables = None                 # `regions=` prompts: (geometry, row table, column table) of psalm_mask_resize_nearest_pad on the device
 
     def nbytes(self) -> int:
         """device bytes held: vision tensors + K / V fronts + prefix cache (2 * layers * P * hidden * 4 up to padding)"""
@@ -1712,17 +1724,178 @@ class PSALM:
                 outs.append(r)
         return outs
 
+    # ---- region prompts given as geometry (`regions=` of segment / segment_many): the dataset mapper's host preparation of a click -- draw the prompt,
+    # enhance_with_circles, apply_segmentation, nonzero() (coco_instance_mapper.py:233-252, context_cluster.py:345-356) -- on the device.  The host
+    # validates and packs a primitive table; psalm_mask_rasterize / psalm_mask_dilate_disc / psalm_mask_resize_nearest_pad make the (S, S) region masks
+    # the host path would have uploaded; ONE read-back brings the R pixel totals the sampler needs; psalm_mask_select_points turns its ranks into the
+    # points `region_points` would have computed, bit for bit.
+    REGION_PROMPT_KEYS = ("points", "scribble", "box", "mask", "rle")
+    REGION_PROMPT_RADIUS = {"points": 10, "scribble": 5}              # coco_instance_mapper.py:247-250
+    REGION_PROMPT_MAX_RADIUS = 16
+
+    def _region_prompt_plan(self, session, input_ids, seg_info, regions, tag=""):
+        """Host side of `regions=` for the N prompts of one session: validation (ValueError naming prompt and region) and the arrays that travel in
+        the call's blob under names ending in `tag` -- the primitive table (n, 6) int32, the radii (R) int32 (-1: not dilated), host mask prompts,
+        the all-zero image index of region_pool.  R = all regions of the N prompts, prompt by prompt."""
+        from .preprocess import rle_to_mask
+        if self.seg_task != "region":
+            raise ValueError(f"regions are prompts of the region task (this model's seg_task = {self.seg_task!r})")
+        tr = session.seg_info.get("transforms") if isinstance(session.seg_info, dict) else None
+        if tr is None:
+            raise ValueError("regions need the session's seg_info['transforms'] (the resize / pad record of the image: encode_image(images, seg_info))")
+        h, w, nh, nw = [int(v) for v in tr["resize"]]
+        ph, pw = [int(v) for v in tr["pad"]]
+        Hi, Wi = int(session.images.shape[2]), int(session.images.shape[3])
+        if (nh + ph, nw + pw) != (Hi, Wi):
+            raise ValueError(f"the session's transforms lead to {(nh + ph, nw + pw)}, its image is {(Hi, Wi)}")
+        N = int(input_ids.shape[0])
+        if not isinstance(regions, (list, tuple)) or len(regions) != N:
+            raise ValueError(f"regions: one list of region prompts per prompt ({N} prompts)")
+        n_tok = (input_ids == REGION_TOKEN_INDEX).sum(1).tolist()
+        prims, radii, masks, counts = [], [], [], []
+
+        def coord(v, what, where):
+            if isinstance(v, (bool, np.bool_)) or not isinstance(v, (int, np.integer)):
+                raise ValueError(f"{where}: {what} {v!r} is not an integer pixel coordinate")
+            return int(v)
+
+        for b, entry in enumerate(regions):
+            if not isinstance(entry, (list, tuple)) or len(entry) != n_tok[b]:
+                got = len(entry) if isinstance(entry, (list, tuple)) else type(entry).__name__
+                raise ValueError(f"prompt {b}: {got} region prompts for {n_tok[b]} <region> tokens")
+            inst = seg_info[b].get("instances") if isinstance(seg_info[b], dict) else None
+            if getattr(inst, "region_masks", None) is not None:
+                raise ValueError(f"prompt {b}: regions given together with seg_info's instances.region_masks")
+            counts.append(len(entry))
+            for j, rp in enumerate(entry):
+                where = f"prompt {b}, region {j}"
+                g = len(radii)
+                kinds = [k for k in self.REGION_PROMPT_KEYS if isinstance(rp, dict) and k in rp]
+                if len(kinds) != 1:
+                    raise ValueError(f"{where}: a region prompt is a dict with exactly one of {self.REGION_PROMPT_KEYS}, got "
+                                     f"{sorted(rp) if isinstance(rp, dict) else type(rp).__name__}")
+                kind = kinds[0]
+                extra = sorted(set(rp) - {kind} - ({"radius"} if kind in self.REGION_PROMPT_RADIUS else set()))
+                if extra:
+                    raise ValueError(f"{where}: unknown keys {extra} in a {kind!r} prompt")
+                if kind in self.REGION_PROMPT_RADIUS:
+                    rad = rp.get("radius", self.REGION_PROMPT_RADIUS[kind])
+                    if isinstance(rad, (bool, np.bool_)) or not isinstance(rad, (int, np.integer)) or not 0 <= int(rad) <= self.REGION_PROMPT_MAX_RADIUS:
+                        raise ValueError(f"{where}: radius {rad!r} outside 0..{self.REGION_PROMPT_MAX_RADIUS}")
+                    pix = list(rp[kind])
+                    if not pix:
+                        raise ValueError(f"{where}: an empty {kind!r} list")
+                    for p in pix:
+                        if len(p) != 2:
+                            raise ValueError(f"{where}: {p!r} is not a (y, x) pair")
+                        y, x = coord(p[0], "y", where), coord(p[1], "x", where)
+                        if not (0 <= y < h and 0 <= x < w):
+                            raise ValueError(f"{where}: pixel {(y, x)} outside the image of {(h, w)}")
+                        prims.append((g, 0, y, x, 0, 0))
+                    radii.append(int(rad))
+                elif kind == "box":
+                    if len(rp["box"]) != 4:
+                        raise ValueError(f"{where}: a box is (y0, x0, y1, x1)")
+                    y0, x0, y1, x1 = [coord(v, "box coordinate", where) for v in rp["box"]]
+                    if not (0 <= y0 < y1 <= h and 0 <= x0 < x1 <= w):
+                        raise ValueError(f"{where}: box {(y0, x0, y1, x1)} is not 0 <= y0 < y1 <= {h}, 0 <= x0 < x1 <= {w}")
+                    prims.append((g, 1, y0, x0, y1, x1))
+                    radii.append(-1)
+                else:
+                    m = rle_to_mask(rp["rle"]) if kind == "rle" else rp["mask"]
+                    if not torch.is_tensor(m):
+                        m = np.asarray(m)
+                    if tuple(m.shape) != (h, w):
+                        raise ValueError(f"{where}: a mask of shape {tuple(m.shape)} for an image of {(h, w)}")
+                    if m.dtype not in (torch.uint8, torch.bool, np.dtype(np.uint8), np.dtype(np.bool_)):
+                        raise ValueError(f"{where}: a mask of dtype {m.dtype} (uint8 or bool)")
+                    if torch.is_tensor(m) and m.device.type == "cpu":
+                        m = m.numpy()
+                    masks.append((g, m if torch.is_tensor(m) else np.ascontiguousarray(m != 0).view(np.uint8)))
+                    radii.append(-1)
+        R = len(radii)
+        if R == 0:
+            raise ValueError("regions given, but no prompt holds a <region> token")
+        arrays = {f"region_img{tag}": np.zeros(R, np.int32),                                   # every region pools from the session's image
+                  f"region_prims{tag}": np.asarray(prims, np.int32).reshape(-1, 6), f"region_radii{tag}": np.asarray(radii, np.int32)}
+        for g, m in masks:
+            if not torch.is_tensor(m):
+                arrays[f"region_mask{tag}_{g}"] = m.reshape(-1)
+        return {"tag": tag, "R": R, "counts": counts, "hw": (h, w), "tables": (h, w, nh, nw, ph, pw), "masks": masks, "arrays": arrays,
+                "max_radius": max([0] + radii)}
+
+    def _region_prompt_masks(self, session, rp, dv, total):
+        """Device side, in front of the read-back: one launch each of rasterize, dilate and resize + pad for the R regions of `rp`; `total` (R) int32
+        zeroed, receives the pixel totals of the resized masks.  Returns (masks (R, S, S) uint8, row_cnt (R, S))."""
+        o = self.ops
+        tag, R, (h, w) = rp["tag"], rp["R"], rp["hw"]
+        tabs = session.region_tables
+        if tabs is None or tabs[0] != rp["tables"]:
+            from .preprocess import nearest_pad_tables
+            rows, cols = nearest_pad_tables(*rp["tables"])
+            tabs = session.region_tables = (rp["tables"], self._dev_i32(rows), self._dev_i32(cols))
+        raw = o.mask_rasterize(dv[f"region_prims{tag}"].view(-1, 6), R, h, w)
+        for g, m in rp["masks"]:                                  # mask prompts: into their (zeroed) plane as they are
+            if torch.is_tensor(m):
+                m = m.to(self.device).contiguous()
+                src = m.view(torch.uint8) if m.dtype == torch.bool else m
+            else:
+                src = dv[f"region_mask{tag}_{g}"]
+            o.copy_(raw[g], src.view(h, w))
+        dil = o.mask_dilate_disc(raw, dv[f"region_radii{tag}"], rp["max_radius"])
+        return o.mask_resize_nearest_pad(dil, tabs[1], tabs[2], total=total)
+
+    def _region_prompt_ranks(self, rp, totals, sampler):
+        """Behind the read-back: `sampler(m, n)` per region in order (prompt by prompt, region by region) -> (R, n) int32 ranks into each region's
+        non-zero pixels.  A region without a pixel is an error here (the reference would fail in randint(0, 0))."""
+        n = self.cfg.region_points
+        out, g = [], 0
+        for b, k in enumerate(rp["counts"]):
+            for j in range(k):
+                m = int(totals[g])
+                if m <= 0:
+                    raise ValueError(f"prompt {b}, region {j}: no pixel of the prompt is left after the resize to the model's input size")
+                idx = torch.as_tensor(sampler(m, n)).reshape(-1).to(torch.int32)
+                if idx.numel() != n:
+                    raise ValueError(f"prompt {b}, region {j}: the region_index_sampler returned {idx.numel()} ranks, {n} are needed")
+                out.append(idx)
+                g += 1
+        return torch.stack(out) if out else torch.zeros(0, n, dtype=torch.int32)
+
+    def _region_pick(self, res):
+        """`pick=True`: per region the best query (first arg-max of `instances.scores`' column), its score and its binary mask as bytes, from a
+        post-processed region result that `_finalize` has not sliced yet."""
+        o = self.ops
+        _, scores, inst_masks, _ = res["_pending"]
+        q, s = o.region_best(scores if scores.is_contiguous() else scores.contiguous())
+        return {"picked_query": o.to_i64(q), "picked_scores": s, "picked_masks": o.mask_gather_u8(inst_masks, q)}
+
     @torch.no_grad()
     def segment(self, session: "ImageSession", input_ids, attention_mask=None, *, seg_info=None, class_name_ids=None,
                 class_name_embedding_indices=None, cls_indices=None, token_refer_id=None, refer_embedding_indices=None, is_thing_list=None,
                 labels=None, region_point_sampler: Callable = default_region_point_sampler, postprocess: bool = True,
-                stages: Optional[dict] = None):
+                stages: Optional[dict] = None, regions=None, region_index_sampler: Callable = default_region_index_sampler, pick: bool = True):
         """N >= 1 prompts of the model's task on the session's image: what `eval_seg` returns for a batch of N copies of that image with these
         prompts (a list of N result dicts), without running the vision side again and with a Phi pass over the rows behind the shared prefix
         only.  Prompt-side keywords as eval_seg; `seg_info`: per prompt (region masks / ground truth under "instances", geometry), default the
         session's entry for every prompt.  All prompts must agree on the tokens up to and including their one <image> (ValueError otherwise).
         postprocess=False: the predictor outputs per prompt, as `forward_logits`; `stages`: filled as by `forward_logits(stages=...)` with the
-        suffix rows' `inputs_embeds` / `hidden_states`."""
+        suffix rows' `inputs_embeds` / `hidden_states`.
+
+        `regions` (region task): the region prompts as GEOMETRY instead of `instances.region_masks` -- per prompt a list with one dict per <region>
+        token, in pixels of the ORIGINAL image (the (h, w) of the session's `seg_info["transforms"]["resize"]`):
+            {"points": [(y, x), ...]}      discs of radius 10 ("radius": k overrides it, 0..16)
+            {"scribble": [(y, x), ...]}    the stroke's pixels, radius 5 (same override)
+            {"box": (y0, x0, y1, x1)}      half-open, 0 <= y0 < y1 <= h, 0 <= x0 < x1 <= w; not dilated
+            {"mask": (h, w) uint8 / bool array or tensor, host or device}   used as it is (non-zero = set)
+            {"rle": COCO RLE dict}         decoded on the host (preprocess.rle_to_mask), then a mask
+        The prompt is drawn, dilated, resized + padded and sampled on the device (psalm_mask_rasterize, psalm_mask_dilate_disc,
+        psalm_mask_resize_nearest_pad, psalm_mask_select_points: one launch each per call, one read-back of the R pixel totals);
+        `region_index_sampler(m, n)` draws n ranks into the m pixels of a region, prompt by prompt, region by region.  The results equal, bit for
+        bit, those of the host path on `apply_segmentation(enhance_with_circles(mask, radius), transforms)` as `region_masks` under
+        `region_point_sampler = lambda nz, k: region_index_sampler(nz.shape[0], k)`.  With `regions`, `gt` is returned only where the prompt's
+        seg_info carries `instances.gt_masks`, and `pick=True` adds `picked_query` (R) int64, `picked_scores` (R) float32, `picked_masks`
+        (R, H, W) uint8 (device tensors): per region the first arg-max of `instances.scores` and that query's mask."""
         self._session_mode_check()
         if not isinstance(session, ImageSession) or session.model is not self:
             raise ValueError("segment: this session was made by another model (or replica)")
@@ -1742,7 +1915,15 @@ class PSALM:
         n_img = session.n_img
         arrays = {}
         n_regions = None
-        if bool((input_ids == REGION_TOKEN_INDEX).any()):
+        rp = None
+        if regions is not None:
+            try:
+                rp = self._region_prompt_plan(session, input_ids, seg_info, regions)
+            except ValueError as e:
+                raise ValueError(f"segment: {e}") from None
+            n_regions = rp["counts"]
+            arrays.update(rp["arrays"])
+        elif bool((input_ids == REGION_TOKEN_INDEX).any()):
             pts, n_regions = self.region_points([s_["instances"].region_masks.tensor for s_ in seg_info], region_point_sampler)
             arrays["region_img"] = np.zeros(sum(n_regions), np.int32)                 # every region pools from the session's image
             arrays["region_pts"] = np.ascontiguousarray(pts.numpy(), np.float32)
@@ -1755,9 +1936,20 @@ class PSALM:
                 arrays[name + "_off"], arrays[name + "_rows"] = sp[name]
         blob, layout = self._pack(arrays)
         dv = self._views(torch.from_numpy(blob).to(self.device), layout)
+        if rp is not None and rp["R"]:
+            total = o.zeros(rp["R"], dtype=torch.int32)
+            rmasks, row_cnt = self._region_prompt_masks(session, rp, dv, total)
         cache = self._session_prefix(session, sp)
         region_feats = None
-        if n_regions is not None:
+        if rp is not None and rp["R"]:
+            try:
+                idx = self._region_prompt_ranks(rp, total.cpu().tolist(), region_index_sampler)       # the call's ONE read-back before the results
+            except ValueError as e:
+                raise ValueError(f"segment: {e}") from None
+            side = int(math.sqrt(n_img))
+            region_feats = o.region_pool(session.image_tokens, dv["region_img"], o.mask_select_points(rmasks, row_cnt, idx.to(self.device)), side,
+                                         side, n_img)
+        elif n_regions is not None and rp is None:
             side = int(math.sqrt(n_img))
             region_feats = o.region_pool(session.image_tokens, dv["region_img"], dv["region_pts"].view(sum(n_regions), -1, 2), side, side, n_img)
         embeds = o.gather_rows([w["embed"], session.image_tokens, w["seg_query"], region_feats], dv["sid"], dv["srow"], cfg.hidden_size,
@@ -1807,12 +1999,14 @@ class PSALM:
                 outs.append(r)
                 continue
             res = self._postprocess(r, self._post_sizes(Hi, Wi, seg_info[b], cfg.size_divisibility))
-            outs.append(self._finalize(res, seg_info[b]))
+            picked = self._region_pick(res) if rp is not None and pick and n_regions[b] else {}
+            outs.append(self._finalize(res, seg_info[b], gt_optional=rp is not None))
+            outs[-1].update(picked)
         return outs
 
     @torch.no_grad()
     def segment_many(self, requests, *, postprocess: bool = True, region_point_sampler: Callable = default_region_point_sampler,
-                     stages: Optional[dict] = None):
+                     stages: Optional[dict] = None, region_index_sampler: Callable = default_region_index_sampler, pick: bool = True):
         """Prompts on SEVERAL images in one Phi pass: `requests` is a list of (session, kwargs) pairs, kwargs what `segment(session, **kwargs)` takes
         for the prompt side (input_ids, attention_mask, seg_info, class_name_ids, ..., is_thing_list).  Returns one list per request, each what
         `segment(session, **kwargs)` returns.  Every request obeys segment's rules on its own (session of this model and weights version, its
@@ -1823,6 +2017,9 @@ class PSALM:
         predictor and post-processing run per prompt from its own session.
         Region task: `region_point_sampler` is called request by request in list order, inside a request prompt by prompt and region by region --
         the order a loop of `segment` calls over `requests` draws in.
+        A request's kwargs may carry `regions` (and `pick`) as `segment` takes them: the prompt masks are made per request on the device, ONE read-back
+        brings the pixel totals of all requests, and `region_index_sampler` is called request by request, prompt by prompt, region by region.  Either
+        every region request of a call gives `regions` or none does (the two paths draw from the sampler at different points of the call).
         `stages`: filled with the suffix rows' `inputs_embeds` / `hidden_states` ((N, S, hidden), N = all prompts in request order), `prefix_lens`
         (per prompt) and `lengths`."""
         self._session_mode_check()
@@ -1832,6 +2029,7 @@ class PSALM:
         o, w, cfg = self.ops, self.w, self.cfg
         plans, arrays = [], {}
         any_regions = False
+        rps = []                                                  # per request: the plan of its `regions`, or None
         for r, (session, kw) in enumerate(requests):
             if not isinstance(session, ImageSession) or session.model is not self:
                 raise ValueError(f"segment_many: request {r}: this session was made by another model (or replica)")
@@ -1851,7 +2049,16 @@ class PSALM:
             if len(seg_info) != N:
                 raise ValueError(f"segment_many: request {r}: one seg_info entry per prompt")
             n_regions = None
-            if bool((ids == REGION_TOKEN_INDEX).any()):
+            rps.append(None)
+            if kw.get("regions") is not None:
+                try:
+                    rps[r] = self._region_prompt_plan(session, ids, seg_info, kw["regions"], tag=str(r))
+                except ValueError as e:
+                    raise ValueError(f"segment_many: request {r}: {e}") from None
+                n_regions = rps[r]["counts"]
+                arrays.update(rps[r]["arrays"])
+                any_regions = True
+            elif bool((ids == REGION_TOKEN_INDEX).any()):
                 pts, n_regions = self.region_points([s_["instances"].region_masks.tensor for s_ in seg_info], region_point_sampler)
                 arrays[f"region_img{r}"] = np.zeros(sum(n_regions), np.int32)         # every region pools from its own session's image
                 arrays[f"region_pts{r}"] = np.ascontiguousarray(pts.numpy(), np.float32)
@@ -1863,6 +2070,8 @@ class PSALM:
             except ValueError as e:
                 raise ValueError(f"segment_many: request {r}: {e}") from None
             plans.append((session, sp, N, seg_info, n_regions))
+        if any(p is not None for p in rps) and any(p is None and pl[4] is not None for p, pl in zip(rps, plans)):
+            raise ValueError("segment_many: some requests give `regions`, others instances.region_masks: one kind per call")
         for name in ("cls", "refer", "region"):
             if len({sp[name] is None for _, sp, _, _, _ in plans}) != 1:
                 raise ValueError(f"segment_many: some requests carry {name} rows and some do not; all requests are prompts of the model's one task")
@@ -1913,14 +2122,36 @@ class PSALM:
         blob, layout = self._pack(arrays)
         dv = self._views(torch.from_numpy(blob).to(self.device), layout)
         region_feats = None
+        dev_pts = {}
+        if any(p is not None for p in rps):                      # `regions`: masks per request, ONE read-back of all totals, then the sampler in request order
+            total = o.zeros(sum(p["R"] for p in rps if p is not None), dtype=torch.int32)
+            made, g0 = {}, 0
+            for r, p in enumerate(rps):
+                if p is not None:
+                    made[r] = self._region_prompt_masks(plans[r][0], p, dv, total[g0:g0 + p["R"]])
+                    g0 += p["R"]
+            totals = total.cpu().tolist()
+            ranks, g0 = {}, 0
+            for r, p in enumerate(rps):
+                if p is not None:
+                    try:
+                        ranks[r] = self._region_prompt_ranks(p, totals[g0:g0 + p["R"]], region_index_sampler)
+                    except ValueError as e:
+                        raise ValueError(f"segment_many: request {r}: {e}") from None
+                    g0 += p["R"]
+            idx = torch.cat([ranks[r] for r in sorted(ranks)]).to(self.device)
+            g0 = 0
+            for r in sorted(ranks):
+                dev_pts[r] = o.mask_select_points(made[r][0], made[r][1], idx[g0:g0 + rps[r]["R"]])
+                g0 += rps[r]["R"]
         if any_regions:
             feats = []
             for r, (session, sp, N, _, n_regions) in enumerate(plans):
                 if n_regions is None:
                     continue
                 side = int(math.sqrt(session.n_img))
-                feats.append(o.region_pool(session.image_tokens, dv[f"region_img{r}"], dv[f"region_pts{r}"].view(sum(n_regions), -1, 2), side, side,
-                                           session.n_img))
+                pts = dev_pts[r] if r in dev_pts else dv[f"region_pts{r}"].view(sum(n_regions), -1, 2)
+                feats.append(o.region_pool(session.image_tokens, dv[f"region_img{r}"], pts, side, side, session.n_img))
             region_feats = feats[0] if len(feats) == 1 else torch.cat(feats)
         embeds = o.gather_rows([w["embed"], None, w["seg_query"], region_feats], dv["sid"], dv["srow"], cfg.hidden_size, out_dtype=torch.float32)
         hidden = self._llm_session(embeds, dv["kmask"].view(Nt, S), Nt, S, P_max, None, suffix=True, refs=(dv["refs"], rhost))
@@ -1965,7 +2196,7 @@ class PSALM:
             if rs is not None:
                 decoded.update(zip(gs, rs))
         g = 0
-        for session, sp, N, seg_info, n_regions in plans:
+        for ri, (session, sp, N, seg_info, n_regions) in enumerate(plans):
             mf, ms, shapes, mfs = session.mask_features, session.multi_scale_features, session.shapes, session.mask_features_size
             Hi, Wi = int(session.images.shape[2]), int(session.images.shape[3])
             outs = []
@@ -1975,7 +2206,10 @@ class PSALM:
                                                                      kv=self._session_kv(session, n_regions[b] if n_regions else 0))
                 g += 1
                 if postprocess:
-                    res = self._finalize(self._postprocess(res, self._post_sizes(Hi, Wi, seg_info[b], cfg.size_divisibility)), seg_info[b])
+                    res = self._postprocess(res, self._post_sizes(Hi, Wi, seg_info[b], cfg.size_divisibility))
+                    picked = self._region_pick(res) if rps[ri] is not None and requests[ri][1].get("pick", pick) and n_regions[b] else {}
+                    res = self._finalize(res, seg_info[b], gt_optional=rps[ri] is not None)
+                    res.update(picked)
                 outs.append(res)
             results.append(outs)
         return results
@@ -2118,8 +2352,9 @@ class PSALM:
             self._cache[key] = torch.tensor(t[:C], dtype=torch.int32, device=self.device)
         return self._cache[key]
 
-    def _finalize(self, res, info):
-        """One host round trip per image: fetch the data-dependent counts and slice the padded result buffers."""
+    def _finalize(self, res, info, gt_optional=False):
+        """One host round trip per image: fetch the data-dependent counts and slice the padded result buffers.  gt_optional (region prompts given as
+        geometry): `gt` only where the image's entry carries `instances.gt_masks`."""
         res = dict(res)
         pend = res.pop("_pending")
         hw = res.pop("_hw")
@@ -2143,10 +2378,11 @@ class PSALM:
             res["instances"] = Instances(hw, pred_masks=inst_masks, scores=sc, query_index=qq, pred_boxes=boxes)
         else:
             _, scores, inst_masks, boxes = pend
-            gt = info["instances"].gt_masks
-            gt = gt.tensor if hasattr(gt, "tensor") else gt
-            gt = gt.to(self.device, torch.float32).contiguous()
-            res["gt"] = self.ops.resize_planes(gt, hw[0], hw[1], crop=(oh, ow))                              # LP:1458-1461
+            gt = getattr(info.get("instances"), "gt_masks", None) if gt_optional else info["instances"].gt_masks
+            if gt is not None or not gt_optional:
+                gt = gt.tensor if hasattr(gt, "tensor") else gt
+                gt = gt.to(self.device, torch.float32).contiguous()
+                res["gt"] = self.ops.resize_planes(gt, hw[0], hw[1], crop=(oh, ow))                          # LP:1458-1461
             res["instances"] = Instances(hw, pred_masks=inst_masks, scores=scores, pred_boxes=boxes)
         return res
 

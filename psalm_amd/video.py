@@ -31,22 +31,11 @@ from typing import Callable, List, Optional
 import numpy as np
 import torch
 
-from .model import PSALM
+from .model import PSALM, default_region_index_sampler  # noqa: F401  (the sampler lives next to its point-sampler twin; re-exported here)
 from .preprocess import nearest_pad_tables
 
 MAX_OBJECTS = 32          # one bit per object in psalm_video_fuse's per-pixel set
 TOPK = 10                 # eval_davis.py:446
-
-
-def default_region_index_sampler(m: int, n: int) -> torch.Tensor:
-    """`default_region_point_sampler` (context_cluster.py:31-40 rand_sample_repeat) with the number of non-zero pixels as its argument: row indices
-    into a `nonzero()` of m rows.  The same global-RNG calls in the same order."""
-    m = int(m)
-    if m < n:
-        return torch.cat((torch.arange(m), torch.randint(0, m, (n - m,))))
-    if m == n:
-        return torch.arange(m)
-    return torch.randperm(m)[:n]
 
 
 class _Memory:
