@@ -1733,21 +1733,25 @@ class PSALM:
     REGION_PROMPT_RADIUS = {"points": 10, "scribble": 5}              # coco_instance_mapper.py:247-250
     REGION_PROMPT_MAX_RADIUS = 16
 
-    def _region_prompt_plan(self, session, input_ids, seg_info, regions, tag=""):
+    def _region_prompt_plan(self, session, input_ids, seg_info, regions, tag="", transforms=None, canvas=None):
         """Host side of `regions=` for the N prompts of one session: validation (ValueError naming prompt and region) and the arrays that travel in
         the call's blob under names ending in `tag` -- the primitive table (n, 6) int32, the radii (R) int32 (-1: not dilated), host mask prompts,
-        the all-zero image index of region_pool.  R = all regions of the N prompts, prompt by prompt."""
+        the all-zero image index of region_pool.  R = all regions of the N prompts, prompt by prompt.  Without a session (`session=None`, the
+        video tracker): the image's geometry as `transforms` (its resize / pad record) and `canvas` (the (H, W) of the model's input)."""
         from .preprocess import rle_to_mask
         if self.seg_task != "region":
             raise ValueError(f"regions are prompts of the region task (this model's seg_task = {self.seg_task!r})")
-        tr = session.seg_info.get("transforms") if isinstance(session.seg_info, dict) else None
+        if session is not None:
+            transforms = session.seg_info.get("transforms") if isinstance(session.seg_info, dict) else None
+            canvas = (session.images.shape[2], session.images.shape[3])
+        tr, whose = transforms, "session" if session is not None else "frame"
         if tr is None:
             raise ValueError("regions need the session's seg_info['transforms'] (the resize / pad record of the image: encode_image(images, seg_info))")
         h, w, nh, nw = [int(v) for v in tr["resize"]]
         ph, pw = [int(v) for v in tr["pad"]]
-        Hi, Wi = int(session.images.shape[2]), int(session.images.shape[3])
+        Hi, Wi = int(canvas[0]), int(canvas[1])
         if (nh + ph, nw + pw) != (Hi, Wi):
-            raise ValueError(f"the session's transforms lead to {(nh + ph, nw + pw)}, its image is {(Hi, Wi)}")
+            raise ValueError(f"the {whose}'s transforms lead to {(nh + ph, nw + pw)}, its image is {(Hi, Wi)}")
         N = int(input_ids.shape[0])
         if not isinstance(regions, (list, tuple)) or len(regions) != N:
             raise ValueError(f"regions: one list of region prompts per prompt ({N} prompts)")
@@ -1824,12 +1828,13 @@ class PSALM:
         return {"tag": tag, "R": R, "counts": counts, "hw": (h, w), "tables": (h, w, nh, nw, ph, pw), "masks": masks, "arrays": arrays,
                 "max_radius": max([0] + radii)}
 
-    def _region_prompt_masks(self, session, rp, dv, total):
+    def _region_prompt_masks(self, session, rp, dv, total, tables=None):
         """Device side, in front of the read-back: one launch each of rasterize, dilate and resize + pad for the R regions of `rp`; `total` (R) int32
-        zeroed, receives the pixel totals of the resized masks.  Returns (masks (R, S, S) uint8, row_cnt (R, S))."""
+        zeroed, receives the pixel totals of the resized masks.  Returns (masks (R, S, S) uint8, row_cnt (R, S)).  Without a session: `tables`,
+        the (row, column) index tables of `rp["tables"]` on the device."""
         o = self.ops
         tag, R, (h, w) = rp["tag"], rp["R"], rp["hw"]
-        tabs = session.region_tables
+        tabs = (rp["tables"],) + tuple(tables) if session is None else session.region_tables
         if tabs is None or tabs[0] != rp["tables"]:
             from .preprocess import nearest_pad_tables
             rows, cols = nearest_pad_tables(*rp["tables"])

@@ -21,6 +21,11 @@ on the device:
 ONE read-back per step: a block of 1 + 4 R + 2 R^2 32-bit words (flag, pixel counts of the picked and of the resized masks, picks, scores, pair
 counts).  No full-resolution mask crosses the bus unless the caller reads `out`.  Launches are eager (no hipGraph), batch 1.
 
+Without a dataset record (no `instances`, no `vp_images`, no ground truth) a track begins with `start` -- click, box, scribble or mask prompts on
+frame 0 in the grammar of `PSALM.segment(regions=)`, drawn and sampled on the device -- or with `adopt` (masks on an encoded ImageSession), and goes
+on with `track(images, seg_info)`.  The tracker keeps that ORIGIN prompt the way it keeps the memory (frame 0's projector tokens + the resized prompt
+masks), so a frame prompted from it while the memory is empty runs one vision pass too and reads no mask on the host.
+
 Deviation from the reference: when a picked mask is empty -- or has no pixel left after the resize to the model's input size -- the memory is NOT
 replaced (`empty_updates` counts these).  The reference replaces it and then fails in `torch.randint(0, 0, ...)` on the next frame.
 """
@@ -31,7 +36,8 @@ from typing import Callable, List, Optional
 import numpy as np
 import torch
 
-from .model import PSALM, default_region_index_sampler  # noqa: F401  (the sampler lives next to its point-sampler twin; re-exported here)
+from .model import PSALM, ImageSession, default_region_index_sampler  # noqa: F401  (the sampler lives next to its point-sampler twin; re-exported here)
+from .config import REGION_TOKEN_INDEX
 from .preprocess import nearest_pad_tables
 
 MAX_OBJECTS = 32          # one bit per object in psalm_video_fuse's per-pixel set
@@ -48,7 +54,8 @@ class _Memory:
 
 
 class VideoTracker:
-    """See the module docstring.  State: `_mem` (None or the last accepted frame, ~ n_img * hidden * 4 + R * S * S bytes on the device), the clip
+    """See the module docstring.  State: `_mem` (None or the last accepted frame, ~ n_img * hidden * 4 + R * S * S bytes on the device), `_origin`
+    (None or the prompt `start` / `adopt` was given, in the same form) with the tracking prompt's ids, the clip
     name, small cached device tables (resize index tables per geometry, fill numbers), and the counters
         memory_frames      steps prompted from memory
         prompt_frames      steps prompted from the caller's vp_images / vp_region_masks
@@ -69,9 +76,12 @@ class VideoTracker:
         self.memory_frames = self.prompt_frames = self.rejected_updates = self.empty_updates = 0
 
     def reset(self):
-        """Forget the memory: the next step is prompted by the caller's visual prompt (a new clip)."""
+        """Forget the memory: the next step is prompted by the caller's visual prompt (a new clip).  The origin prompt of `start` / `adopt` goes
+        with it: `track` needs a new one."""
         self._mem: Optional[_Memory] = None
         self._video = None
+        self._origin: Optional[_Memory] = None
+        self._prompt = None                                 # (input_ids, attention_mask, canvas (H, W)) of the track begun by start / adopt
 
     # ------------------------------------------------------------------ small cached device tables
     def _tables(self, transforms):
@@ -212,3 +222,172 @@ class VideoTracker:
         out.update(self._observe(stages["image_tokens"], res.pred_masks, res.scores, fill, info["transforms"]))
         out["used_memory"] = use_memory
         return out
+
+    # ------------------------------------------------------------------ tracks that begin with a prompt instead of a dataset record
+    def _track_prompt(self, who, input_ids, attention_mask, R):
+        """the tracking prompt (1, T) with R <region> tokens"""
+        if not torch.is_tensor(input_ids) or input_ids.dim() not in (1, 2) or (input_ids.dim() == 2 and input_ids.shape[0] != 1):
+            raise ValueError(f"VideoTracker.{who}: one prompt, input_ids (1, T) (batch 1)")
+        if input_ids.dim() == 1:
+            input_ids = input_ids[None]
+            attention_mask = attention_mask[None] if attention_mask is not None and attention_mask.dim() == 1 else attention_mask
+        n_tok = int((input_ids == REGION_TOKEN_INDEX).sum())
+        if n_tok != R:
+            raise ValueError(f"VideoTracker.{who}: {R} regions for {n_tok} <region> tokens in input_ids")
+        return input_ids, attention_mask
+
+    def _fill_for(self, who, fill, R):
+        fill = self._fill_list(list(range(1, R + 1)) if fill is None else fill)
+        if len(fill) != R:
+            raise ValueError(f"VideoTracker.{who}: {len(fill)} fill numbers for {R} regions")
+        return fill
+
+    @staticmethod
+    def _frame_info(who, images, seg_info):
+        if images is None or images.dim() != 4 or images.shape[0] != 1 or seg_info is None or len(seg_info) != 1:
+            raise ValueError(f"VideoTracker.{who}: one frame per call (batch 1)")
+        info = seg_info[0]
+        if not isinstance(info, dict) or info.get("transforms") is None:
+            raise ValueError(f"VideoTracker.{who}: seg_info[0]['transforms'] (the frame's resize / pad record) is needed")
+        return info
+
+    @torch.no_grad()
+    def start(self, input_ids, images, seg_info, regions, attention_mask=None, fill=None,
+              region_index_sampler: Callable = default_region_index_sampler):
+        """Frame 0 of a track (batch 1), prompted by GEOMETRY on the frame itself: `regions` is the flat list of R region prompts of the one prompt
+        `input_ids` ((1, T) with R <region> tokens), in the grammar of `PSALM.segment(regions=)` -- {"points"} / {"scribble"} (+ "radius"),
+        {"box"}, {"mask"}, {"rle"} in integer pixels of the ORIGINAL frame, the (h, w) of `seg_info[0]["transforms"]["resize"]`.  `fill`: R fill
+        numbers in 0..255, default 1..R.  `seg_info[0]` needs no `instances`.
+
+        The prompt is drawn, dilated and resized + padded with the frame's tables on the device (one launch each), ONE read-back brings the R pixel
+        totals, `region_index_sampler(m, n)` is called per region in order, and the <region> features pool from the frame's own projector tokens:
+        one Swin + projector pass.  The result equals, bit for bit, `step` on a fresh tracker with `vp_images = images`,
+        `vp_region_masks = apply_segmentation(mask, transforms)` of the same prompts and `vp_fill_number = fill`; it has the keys of `step`
+        without `gt`.  The tracker keeps the prompt (frame 0's tokens, the resized masks, their counts, `fill`) as the ORIGIN of the track next to
+        the memory, and `input_ids` / `attention_mask` for `track`.  Calling `start` again (a re-prompt on a later frame) replaces origin and memory
+        and resets no counter; a call that raises leaves the tracker as it was."""
+        m, o = self.model, self.ops
+        info = self._frame_info("start", images, seg_info)
+        if not isinstance(regions, (list, tuple)):
+            raise ValueError("VideoTracker.start: regions is a list with one region prompt per <region> token")
+        R = len(regions)
+        input_ids, attention_mask = self._track_prompt("start", input_ids, attention_mask, R)
+        fill = self._fill_for("start", fill, R)
+        tr = info["transforms"]
+        images = images.to(m.device, torch.float32).contiguous()
+        canvas = (int(images.shape[2]), int(images.shape[3]))
+        try:
+            rp = m._region_prompt_plan(None, input_ids, [info], [list(regions)], transforms=tr, canvas=canvas)
+        except ValueError as e:
+            raise ValueError(f"VideoTracker.start: {e}") from None
+        extra = {k: v for k, v in rp["arrays"].items() if k != "region_img"}                  # (_prepare writes the image index itself)
+        blob, layout, meta = m._prepare(input_ids, attention_mask, images, [info], None, None, None, None, None, None, video=True,
+                                        region_counts=[R], extra_arrays=extra)
+        dv = m._views(torch.from_numpy(blob).to(m.device), layout)
+        total = o.zeros(R, dtype=torch.int32)
+        masks, row_cnt = m._region_prompt_masks(None, rp, dv, total, tables=self._tables(tr))
+        counts = total.cpu().tolist()                                                         # the ONE read-back in front of the model pass
+        try:
+            idx = m._region_prompt_ranks(rp, counts, region_index_sampler)
+        except ValueError as e:
+            raise ValueError(f"VideoTracker.start: {e}") from None
+        pts = o.mask_select_points(masks, row_cnt, idx.to(m.device))
+        stages: dict = {}
+        results = m._forward_device(images, dv, meta, stages=stages, region_pts=pts)          # (<region> features from the frame's OWN tokens)
+        out = m._finalize(results[0], info, gt_optional=True)
+        out.pop("gt", None)
+        res = out["instances"]
+        tokens = stages["image_tokens"]
+        keep = o.empty(*tokens.shape, dtype=tokens.dtype)
+        o.copy_(keep, tokens)
+        self._origin = _Memory(keep, masks, row_cnt, [int(c) for c in counts], fill)
+        self._prompt = (input_ids, attention_mask, canvas)
+        self._mem = None
+        self.prompt_frames += 1
+        out.update(self._observe(tokens, res.pred_masks, res.scores, fill, tr))
+        out["used_memory"] = False
+        return out
+
+    @torch.no_grad()
+    def track(self, images, seg_info, region_index_sampler: Callable = default_region_index_sampler):
+        """The next frame (batch 1) of the track begun by `start` / `adopt`: `seg_info[0]` carries the frame's geometry (`transforms`, `height` /
+        `width`, `padding_mask`) and needs no `instances`; no `vp_images`.  With a non-empty memory this is the memory path of `step`; while the
+        memory is empty (the picks of the start frame were rejected or came out empty) the frame is prompted from the kept origin through the
+        same code -- its tokens as `vp_tokens`, points selected on its masks on the device -- and counts as a prompt frame.  One vision pass either
+        way; `region_index_sampler(m, n)` is drawn per region, in order.  Returns the keys of `step` without `gt`.  `file_name` is not read: a
+        new clip begins with `start` or `reset()`."""
+        m, o = self.model, self.ops
+        if self._origin is None:
+            raise ValueError("VideoTracker.track: no track to go on with (call start or adopt first)")
+        info = self._frame_info("track", images, seg_info)
+        input_ids, attention_mask, canvas = self._prompt
+        if (int(images.shape[2]), int(images.shape[3])) != canvas:
+            raise ValueError(f"VideoTracker.track: a frame of {tuple(images.shape[2:])}, the track began on {canvas} (the kept tokens are of that size)")
+        mem = self._mem
+        use_memory = mem is not None and len(mem.fill) == len(self._origin.fill)
+        src = mem if use_memory else self._origin
+        fill = src.fill
+        images = images.to(m.device, torch.float32).contiguous()
+        R, n = len(fill), m.cfg.region_points
+        idx = torch.stack([region_index_sampler(c, n) for c in src.counts]).to(torch.int32)
+        blob, layout, meta = m._prepare(input_ids, attention_mask, images, [info], None, None, None, None, None, None, video=True,
+                                        region_counts=[R], extra_arrays={"region_idx": idx.numpy()})
+        dv = m._views(torch.from_numpy(blob).to(m.device), layout)
+        pts = o.mask_select_points(src.masks, src.row_cnt, dv["region_idx"].view(R, n))
+        stages: dict = {}
+        results = m._forward_device(images, dv, meta, stages=stages, vp_tokens=src.tokens, region_pts=pts)
+        if use_memory:
+            self.memory_frames += 1
+        else:
+            self.prompt_frames += 1
+        out = m._finalize(results[0], info, gt_optional=True)
+        out.pop("gt", None)
+        res = out["instances"]
+        out.update(self._observe(stages["image_tokens"], res.pred_masks, res.scores, fill, info["transforms"]))
+        out["used_memory"] = use_memory
+        return out
+
+    @torch.no_grad()
+    def adopt(self, session, masks, input_ids, attention_mask=None, fill=None):
+        """Go on from an image session's result: `session` is an ImageSession of this model (and weights version) whose `seg_info` has `transforms`,
+        `masks` (R, h, w) uint8 / bool on the device or the host at the session's ORIGINAL size -- `out["picked_masks"]` of
+        `segment(session, ids, regions=..., pick=True)`, or any masks of that size (non-zero = set; the bytes are kept as they are).  They are resized
+        with the session's tables (psalm_mask_resize_nearest_pad; one read-back of the R totals), `session.image_tokens` are copied, and the result
+        becomes both memory and origin of the track: the next `track` is a memory step, equal to `step` with the session's image as `vp_images`
+        and `apply_segmentation(mask, transforms)` as `vp_region_masks`.  `input_ids` (1, T): the tracking prompt with R <region> tokens; `fill`
+        as in `start`.  Runs no model pass and changes no counter; a call that raises leaves the tracker as it was."""
+        m, o = self.model, self.ops
+        if not isinstance(session, ImageSession) or session.model is not m:
+            raise ValueError("VideoTracker.adopt: this session was made by another model (or replica)")
+        if session.version != m._weights_version:
+            raise ValueError("VideoTracker.adopt: the model's weights were prepared again after this session was made; encode the image again")
+        tr = session.seg_info.get("transforms") if isinstance(session.seg_info, dict) else None
+        if tr is None:
+            raise ValueError("VideoTracker.adopt: the session's seg_info['transforms'] (the resize / pad record of its image) is needed")
+        h, w, nh, nw = [int(v) for v in tr["resize"]]
+        canvas = (int(session.images.shape[2]), int(session.images.shape[3]))
+        if (nh + int(tr["pad"][0]), nw + int(tr["pad"][1])) != canvas:
+            raise ValueError(f"VideoTracker.adopt: the session's transforms lead to {(nh + int(tr['pad'][0]), nw + int(tr['pad'][1]))}, "
+                             f"its image is {canvas}")
+        if not torch.is_tensor(masks):
+            masks = torch.from_numpy(np.ascontiguousarray(masks))
+        if masks.dim() != 3 or tuple(masks.shape[1:]) != (h, w):
+            raise ValueError(f"VideoTracker.adopt: masks of shape {tuple(masks.shape)} for an image of {(h, w)} (R, h, w)")
+        if masks.dtype not in (torch.uint8, torch.bool):
+            raise ValueError(f"VideoTracker.adopt: masks of dtype {masks.dtype} (uint8 or bool)")
+        R = int(masks.shape[0])
+        input_ids, attention_mask = self._track_prompt("adopt", input_ids, attention_mask, R)
+        fill = self._fill_for("adopt", fill, R)
+        masks = masks.to(m.device).contiguous()
+        masks = masks.view(torch.uint8) if masks.dtype == torch.bool else masks
+        row_tab, col_tab = self._tables(tr)
+        total = o.zeros(R, dtype=torch.int32)
+        small, row_cnt = o.mask_resize_nearest_pad(masks, row_tab, col_tab, total=total)
+        keep = o.empty(*session.image_tokens.shape, dtype=session.image_tokens.dtype)
+        o.copy_(keep, session.image_tokens)
+        counts = [int(c) for c in total.cpu().tolist()]
+        for r, c in enumerate(counts):
+            if c <= 0:
+                raise ValueError(f"VideoTracker.adopt: region {r}: no pixel of the mask is left after the resize to the model's input size")
+        self._origin = self._mem = _Memory(keep, small, row_cnt, counts, fill)
+        self._prompt = (input_ids, attention_mask, canvas)
