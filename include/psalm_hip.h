@@ -38,8 +38,9 @@ const char* psalm_last_error(void);
  *    psalm_phi_suffix_grouped (+ _workspace).
  * 11: the mask decoder over all prompts of an image session: psalm_mha_attention_f32_shared (+ _workspace), psalm_gemm_f32_rows[_pair],
  *    psalm_gemm_f32_grouped, psalm_predictor_kv_bytes, the stage-level psalm_predictor_forward_batched (+ _workspace).
- * 12: region prompts of image sessions: psalm_mask_rasterize, psalm_mask_dilate_disc, psalm_region_best, psalm_mask_gather_u8. */
-#define PSALM_ABI_VERSION 12
+ * 12: region prompts of image sessions: psalm_mask_rasterize, psalm_mask_dilate_disc, psalm_region_best, psalm_mask_gather_u8.
+ * 13: boxes and areas from masks: psalm_mask_boxes (+ _workspace), psalm_label_boxes. */
+#define PSALM_ABI_VERSION 13
 int psalm_abi_version(void);
 const char* psalm_backend(void); /* "hip-gfx950" */
 
@@ -765,6 +766,27 @@ int psalm_region_best(const float* scores, int Q, int R, int* best_query, float*
 /* out (R,HW) u8: out[r][p] = masks[query[r]][p] > 0 (psalm_binarize_gather's test, one byte per pixel); masks (Q,HW) f32, query (R) i32 on the device,
  * an entry outside [0, Q) gives an empty mask. */
 int psalm_mask_gather_u8(const float* masks, const int* query, int Q, int R, long HW, unsigned char* out, void* stream);
+
+/* ------------------------------------------------------------------------------------------------------------------
+ * Boxes and areas from masks (csrc/maskbox.hip; PSALM.mask_boxes, psalm_amd/evalout.py mask_boxes / label_boxes): the line the reference leaves
+ * commented out as slow on the host, `BitMasks(mask_pred > 0).get_bounding_boxes()` (llava_phi.py:319,395,438-440), as one pass over masks that are
+ * on the device already.  Integer results combined with integer max / add atomics: exact and independent of the order of arrival; nothing
+ * allocates or synchronises. */
+/* masks (n,H,W) contiguous, float32 (dtype_is_u8 = 0; a pixel is set when f > 0 -- psalm_binarize_gather's test: NaN, -0.0 and negatives are not)
+ * or bytes (dtype_is_u8 = 1; set when != 0).  Output row i describes plane index_dev[i] (m entries, int32 on the device; an entry outside [0, n)
+ * gives the empty result), or plane i when index_dev is NULL (then m must equal n):
+ *   boxes (m,4) f32 = (x_min, y_min, x_max + 1, y_max + 1) over the set pixels -- detectron2 BitMasks.get_bounding_boxes -- (0,0,0,0) when none is set;
+ *   areas (m) i32   = number of set pixels.
+ * H * W < 2^31, H, W <= 2^24, m <= 65535; m == 0 is a no-op (n == 0 without an index list therefore too); rows and plane bases need no alignment
+ * beyond the element's own.  workspace: psalm_mask_boxes_workspace(m) bytes (-1: bad m), 4-byte aligned; zeroed by the call itself (a memset node
+ * on `stream`). */
+long psalm_mask_boxes_workspace(int m);
+int psalm_mask_boxes(const void* masks, int dtype_is_u8, int n, int H, int W, const int* index_dev, int m, float* boxes, int* areas, void* workspace,
+                     long workspace_bytes, void* stream);
+/* labels (H,W) contiguous, int32 (dtype_is_u8 = 0) or bytes (1) -> table (n_ids,5) i32: row v = [x0, y0, x1, y1, area] of the pixels whose label
+ * is v, the same box convention; all zeros for a value that does not occur; label values outside [0, n_ids) are ignored.  1 <= n_ids <= 256,
+ * H * W < 2^31.  `table` is zeroed by the call itself (a memset node on `stream`) and serves as the accumulator: no workspace. */
+int psalm_label_boxes(const void* labels, int dtype_is_u8, int H, int W, int n_ids, int* table, void* stream);
 
 #ifdef __cplusplus
 }

@@ -13,6 +13,8 @@ with one tiny RCCL all-reduce (`psalm_amd.dist.reduce_metrics`, the role of Aver
     iou_counts(pred_masks, gt_masks, pairs)       referring_segmentation.py:101-113 (intersectionAndUnionGPU, K=2) -> intersection, union
     fuse_masks_by_score(pred_masks, scores, thr)  eval_grefcoco.py:113-131,277-285 (gRefCOCO: union of the candidates above thr, else top-1)
     IoUMeters                                     referring_segmentation.py:139-177 + :58-79 (cIoU / gIoU bookkeeping + all-reduce)
+    mask_boxes(masks) / label_boxes(labels, n)    llava_phi.py:319,395,438-440 (the commented-out `BitMasks(..).get_bounding_boxes()`) -> boxes, areas
+    coco_instance_records(instances, image_id)    detectron2 instances_to_coco_json (instance_evaluation.py) -> the COCO result records
 """
 from __future__ import annotations
 
@@ -181,6 +183,48 @@ def fuse_masks_by_score(pred_masks: torch.Tensor, scores: torch.Tensor, thr: flo
     return out
 
 
+def mask_boxes(masks: torch.Tensor, ops=None) -> Tuple[torch.Tensor, torch.Tensor]:
+    """Where each mask is and how large: masks (n,H,W) float32 (set: > 0) | uint8 | bool (set: != 0) -> (boxes (n,4) float32, areas (n) int32) on
+    the device.  detectron2's `BitMasks.get_bounding_boxes` -- the line the reference comments out as slow on the host (llava_phi.py:319,395,
+    438-440): (x_min, y_min, x_max + 1, y_max + 1) over the set pixels, zeros for an empty mask; area = set pixels.  Nothing is read back."""
+    o = _ops(ops)
+    if not torch.is_tensor(masks) or masks.dim() != 3:
+        raise H.PsalmHipError("mask_boxes: (n,H,W) float32 / uint8 / bool masks")
+    return o.mask_boxes(_on_device(o, masks, (torch.float32, torch.uint8, torch.bool), "mask_boxes"))
+
+
+def label_boxes(labels: torch.Tensor, n_ids: int, ops=None) -> torch.Tensor:
+    """An id map (H,W) int32 | uint8 -- `panoptic_seg[0]`, the tracker's `fused` -- -> (n_ids,5) int32 on the device: [x0, y0, x1, y1, area] of
+    the pixels of every id in [0, n_ids), n_ids <= 256 (the box convention of `mask_boxes`; zeros for an id that does not occur; other values
+    are ignored)."""
+    o = _ops(ops)
+    if not torch.is_tensor(labels) or labels.dim() != 2:
+        raise H.PsalmHipError("label_boxes: an (H,W) int32 / uint8 id map")
+    return o.label_boxes(_on_device(o, labels, (torch.int32, torch.uint8), "label_boxes"), n_ids)
+
+
+def coco_instance_records(instances, image_id, category_ids: Optional[Sequence[int]] = None, ops=None) -> List[dict]:
+    """detectron2's `instances_to_coco_json`, the records the reference's instance evaluator collects (instance_evaluation.py): per instance
+    {"image_id", "category_id", "bbox": [x, y, w, h] floats from `pred_boxes` (BoxMode XYXY_ABS -> XYWH_ABS), "score", "segmentation": COCO RLE
+    with its counts as str}.  category_ids: the contiguous class index -> dataset category id table (the evaluator's reverse id mapping).
+    Only the small arrays (boxes, scores, classes, run boundaries) are read back; the boxes are real under `PSALM.mask_boxes = True`."""
+    n = len(instances)
+    if n == 0:
+        return []
+    boxes = instances.pred_boxes.detach().cpu().numpy().astype(np.float64)
+    boxes[:, 2] -= boxes[:, 0]
+    boxes[:, 3] -= boxes[:, 1]
+    scores = instances.scores.detach().cpu().tolist()
+    classes = instances.pred_classes.detach().cpu().tolist() if hasattr(instances, "pred_classes") else [0] * n
+    rles = masks_to_rle(instances.pred_masks, ops=ops)
+    out = []
+    for k in range(n):
+        rle = {"size": rles[k]["size"], "counts": rles[k]["counts"].decode("utf-8")}
+        out.append({"image_id": image_id, "category_id": int(category_ids[classes[k]]) if category_ids is not None else int(classes[k]),
+                    "bbox": boxes[k].tolist(), "score": float(scores[k]), "segmentation": rle})
+    return out
+
+
 class IoUMeters:
     """The three AverageMeters of the referring / region evaluation loops (referring_segmentation.py:139-177: intersection, union,
     acc_iou) fed from device-side counts; `all_reduce()` = AverageMeter.all_reduce (:58-79) as ONE small SUM all-reduce."""
@@ -221,6 +265,7 @@ def compact_results(result: dict, gt_sem: Optional[torch.Tensor] = None, conf: O
         "sem_labels"   (H,W) int32          from result["sem_seg"]           (+ conf.update(labels, gt_sem) when both are given)
         "panoptic_rgb" (H,W,3) uint8, "segments_info"   from result["panoptic_seg"]
         "instances"    {"rle": [...], "scores": (n,), "pred_classes": (n,)}  from result["instances"]
+                       (+ "boxes" (n,4), "areas" (n,) when the result was made under `PSALM.mask_boxes = True`)
     Keys follow what the result holds (semantic-only / instance-only tasks give the matching subset)."""
     o = _ops(ops)
     out = {}
@@ -237,4 +282,6 @@ def compact_results(result: dict, gt_sem: Optional[torch.Tensor] = None, conf: O
         out["instances"] = {"rle": masks_to_rle(inst.pred_masks, ops=o), "scores": inst.scores}
         if hasattr(inst, "pred_classes"):
             out["instances"]["pred_classes"] = inst.pred_classes
+        if hasattr(inst, "pred_areas"):
+            out["instances"]["boxes"], out["instances"]["areas"] = inst.pred_boxes, inst.pred_areas
     return out

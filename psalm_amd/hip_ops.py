@@ -49,7 +49,7 @@ def _dt(t: torch.Tensor) -> int:
         raise PsalmHipError(f"unsupported dtype {t.dtype} (float32 / bfloat16 only)")
 
 
-ABI_VERSION = 12       # == PSALM_ABI_VERSION of include/psalm_hip.h (tests/test_0_abi.py compares the two and the built library's answer)
+ABI_VERSION = 13       # == PSALM_ABI_VERSION of include/psalm_hip.h (tests/test_0_abi.py compares the two and the built library's answer)
 
 
 class _ProfiledLib:
@@ -777,10 +777,11 @@ class Ops:
     POST_TASKS = {"semantic": 0, "instance": 1, "panoptic": 2, "referring": 3, "region": 4}
 
     def postprocess(self, task, sizes, pred_masks=None, mask_up=None, cls_logits=None, seg_logits=None, region_logits=None, is_thing=None,
-                    obj_thr=0.8, overlap_thr=0.8):
+                    obj_thr=0.8, overlap_thr=0.8, counts_extra=0):
         """llava_phi.py:1401-1466 for one image as ONE native call (psalm_postprocess_<task>): sizes = (Hpad, Wpad, crop_h, crop_w, out_h, out_w);
         pred_masks (Q,h,w) and / or mask_up (Q,Hpad,Wpad) float32.  Returns a dict of the result tensors at their maximum sizes (the caller slices by
-        `counts` after its one read-back): mask_pred, sem_seg, scores, classes, query, inst_masks, boxes, pan, counts -- those the task has."""
+        `counts` after its one read-back): mask_pred, sem_seg, scores, classes, query, inst_masks, boxes, pan, counts -- those the task has.
+        counts_extra: int32 words allocated behind the 2 + 3 Q the call writes (the caller's own small results, fetched with the same read-back)."""
         Hpad, Wpad, oh, ow, height, width = [int(v) for v in sizes]
         src = pred_masks if pred_masks is not None else mask_up
         Q = int(src.shape[0])
@@ -807,7 +808,7 @@ class Ops:
             out["scores"] = self.empty(Q, k) if task == "region" else self.empty(Q)
             out["inst_masks"] = self.empty(Q, height, width)
             out["boxes"] = self.empty(Q, 4)
-            out["counts"] = self.empty(2 + 3 * Q, dtype=torch.int32)
+            out["counts"] = self.empty(2 + 3 * Q + int(counts_extra), dtype=torch.int32)
             if task in ("instance", "panoptic"):
                 out["classes"] = self.empty(Q, dtype=torch.int64)
             if task != "region":
@@ -1826,6 +1827,51 @@ class Ops:
         rc = self.lib.psalm_mask_gather_u8(self._p(masks), self._p(query), Q, R, c_long(Hh * Ww), self._p(out), self._stream())
         self._check(rc, "psalm_mask_gather_u8")
         return out
+
+    # ------------------------------------------------------------------ boxes and areas from masks (csrc/maskbox.hip)
+    def mask_boxes(self, masks, index=None, out_boxes=None, out_areas=None, workspace=None):
+        """masks (n,H,W) float32 (set: > 0) | uint8 / bool (set: != 0) -> (boxes (m,4) f32 = (x_min, y_min, x_max + 1, y_max + 1), zeros for an empty
+        mask; areas (m) i32 = set pixels): psalm_mask_boxes.  index (m) i32 on the device: the planes to describe (an entry outside [0, n) gives the
+        empty result), default all n in order.  The outputs may be given (views of a caller-owned block); workspace: a caller's uint8 buffer of
+        psalm_mask_boxes_workspace(m) bytes instead of the binding's cached one."""
+        if masks.dim() != 3 or masks.dtype not in (torch.float32, torch.uint8, torch.bool):
+            raise PsalmHipError(f"mask_boxes: masks (n,H,W) float32 / uint8 / bool, got {masks.dtype} {tuple(masks.shape)}")
+        if masks.dtype == torch.bool:
+            masks = masks.view(torch.uint8)
+        n, Hh, Ww = masks.shape
+        m = n if index is None else int(index.numel())
+        if index is not None:
+            self._want(index, torch.int32, (m,), "mask_boxes index")
+        boxes = self.empty(m, 4) if out_boxes is None else self._want(out_boxes, torch.float32, (m, 4), "mask_boxes out_boxes")
+        areas = self.empty(m, dtype=torch.int32) if out_areas is None else self._want(out_areas, torch.int32, (m,), "mask_boxes out_areas")
+        self.lib.psalm_mask_boxes_workspace.restype = c_long
+        nbytes = self.lib.psalm_mask_boxes_workspace(m)
+        if nbytes < 0:
+            raise PsalmHipError(f"mask_boxes: {m} output rows (at most 65535)")
+        if workspace is None:
+            ws, have = self._stage_ws("mask_boxes", max(nbytes, 4)), nbytes
+        else:
+            if workspace.dtype != torch.uint8:
+                raise PsalmHipError("mask_boxes: workspace must be a uint8 buffer")
+            ws, have = workspace, int(workspace.numel())
+        rc = self.lib.psalm_mask_boxes(self._p(masks), 1 if masks.dtype == torch.uint8 else 0, n, Hh, Ww, self._p(index), m, self._p(boxes),
+                                       self._p(areas), self._p(ws), c_long(have), self._stream())
+        self._check(rc, "psalm_mask_boxes")
+        return boxes, areas
+
+    def label_boxes(self, labels, n_ids, out=None):
+        """labels (H,W) int32 | uint8 -> table (n_ids,5) i32 of [x0, y0, x1, y1, area] per label value in [0, n_ids) (zeros for an absent value;
+        other values are ignored), 1 <= n_ids <= 256: psalm_label_boxes.  `out` may be given (a view of a caller-owned block)."""
+        if labels.dim() != 2 or labels.dtype not in (torch.int32, torch.uint8):
+            raise PsalmHipError(f"label_boxes: labels (H,W) int32 / uint8, got {labels.dtype} {tuple(labels.shape)}")
+        n_ids = int(n_ids)
+        if not 1 <= n_ids <= 256:
+            raise PsalmHipError(f"label_boxes: n_ids = {n_ids} (1..256)")
+        Hh, Ww = labels.shape
+        table = self.empty(n_ids, 5, dtype=torch.int32) if out is None else self._want(out, torch.int32, (n_ids, 5), "label_boxes out")
+        rc = self.lib.psalm_label_boxes(self._p(labels), 1 if labels.dtype == torch.uint8 else 0, Hh, Ww, n_ids, self._p(table), self._stream())
+        self._check(rc, "psalm_label_boxes")
+        return table
 
 
 _OPS: Optional[Ops] = None

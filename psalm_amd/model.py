@@ -48,7 +48,7 @@ from .config import (CLS_TOKEN_INDEX, IMAGE_TOKEN_INDEX, REFER_TOKEN_INDEX, REGI
 
 class Instances:
     """Result container with the attribute surface the reference's evaluators read from detectron2 `Instances`
-    (LP:317-323, LP:435-447): image_size, pred_masks, scores, pred_classes, pred_boxes."""
+    (LP:317-323, LP:435-447): image_size, pred_masks, scores, pred_classes, pred_boxes (+ pred_areas under `PSALM.mask_boxes`)."""
 
     def __init__(self, image_size, **fields):
         self.image_size = tuple(image_size)
@@ -58,6 +58,10 @@ class Instances:
 
     def has(self, name):
         return name in self._fields
+
+    def set(self, name, value):
+        self._fields[name] = value
+        setattr(self, name, value)
 
     def get_fields(self):
         return self._fields
@@ -194,6 +198,11 @@ class PSALM:
         self.c_stages = True
         self.kv_side = True        # r06: the predictor's K / V front on the side stream beside the LLM (False: at the start of the predictor call, as r05; A/B switch)
         self.graph_tail = False
+        # True: `instances.pred_boxes` holds the boxes of the returned masks (the line the reference leaves commented out as slow on the host,
+        # `BitMasks(mask_pred > 0).get_bounding_boxes()`, LP:319,395,438-440) and `instances.pred_areas` their pixel counts, panoptic segments
+        # carry "area" / "bbox", picks carry `picked_boxes` / `picked_areas`, the tracker returns `boxes`: one psalm_mask_boxes pass (csrc/
+        # maskbox.hip) over masks that are on the device already.  False (default): the reference's all-zero boxes, no extra launch.
+        self.mask_boxes = False
         self.graph_stats = {"calls": 0, "replays": 0, "eager": 0, "captures": 0}
         self.use_graphs = use_graphs                  # capture each input signature's launch sequence into a hipGraph
         # Graph replay writes its results into buffers owned by the captured graph; "copy" (default) hands the caller private copies,
@@ -291,11 +300,12 @@ class PSALM:
 
     @classmethod
     def from_pretrained(cls, model_path, mask_decoder_cfg=None, *, precision: Optional[str] = None, use_graphs: bool = True, ops=None,
-                        seg_task: Optional[str] = None, **hf_kwargs):
+                        seg_task: Optional[str] = None, mask_boxes: bool = False, **hf_kwargs):
         """`PSALM.from_pretrained(model_path, mask_decoder_cfg=mask_cfg, **kwargs)` (psalm/model/builder.py:54): Hugging Face checkpoint
         directory -> model.  `mask_decoder_cfg`: the (attribute-style) mask YAML the reference passes, or None for the released
         defaults.  The Hugging Face loader keywords the reference passes (torch_dtype, device_map, low_cpu_mem_usage ...) are accepted
-        and ignored; bitsandbytes quantisation is rejected.  `precision`, `use_graphs`, `ops`, `seg_task` are extensions."""
+        and ignored; bitsandbytes quantisation is rejected.  `precision`, `use_graphs`, `ops`, `seg_task`, `mask_boxes` (see the
+        attribute) are extensions."""
         from . import builder as B
         from .config import load_mask_config
         if hf_kwargs.get("load_in_8bit") or hf_kwargs.get("load_in_4bit") or hf_kwargs.get("quantization_config") is not None:
@@ -305,6 +315,7 @@ class PSALM:
         cfg = B.config_from_hf(model_path, mask_cfg, task)
         model = cls(cfg, B.read_checkpoint(model_path), ops=ops, precision=precision or cls.DEFAULT_PRECISION, use_graphs=use_graphs)
         model.config = B.hf_config(model_path)
+        model.mask_boxes = bool(mask_boxes)
         m = mask_cfg.MODEL
         proc = B.ImagePreprocessor(mask_cfg.INPUT.IMAGE_SIZE, m.PIXEL_MEAN, m.PIXEL_STD, device=None)
         model.image_processor = {"panoptic": proc, "instance": proc, "semantic": proc}             # llava_phi.py:66-69
@@ -1873,7 +1884,10 @@ class PSALM:
         o = self.ops
         _, scores, inst_masks, _ = res["_pending"]
         q, s = o.region_best(scores if scores.is_contiguous() else scores.contiguous())
-        return {"picked_query": o.to_i64(q), "picked_scores": s, "picked_masks": o.mask_gather_u8(inst_masks, q)}
+        out = {"picked_query": o.to_i64(q), "picked_scores": s, "picked_masks": o.mask_gather_u8(inst_masks, q)}
+        if self.mask_boxes:                      # the picked queries' planes through the index list: no gather copy
+            out["picked_boxes"], out["picked_areas"] = o.mask_boxes(inst_masks, index=q)
+        return out
 
     @torch.no_grad()
     def segment(self, session: "ImageSession", input_ids, attention_mask=None, *, seg_info=None, class_name_ids=None,
@@ -1900,7 +1914,8 @@ class PSALM:
         bit, those of the host path on `apply_segmentation(enhance_with_circles(mask, radius), transforms)` as `region_masks` under
         `region_point_sampler = lambda nz, k: region_index_sampler(nz.shape[0], k)`.  With `regions`, `gt` is returned only where the prompt's
         seg_info carries `instances.gt_masks`, and `pick=True` adds `picked_query` (R) int64, `picked_scores` (R) float32, `picked_masks`
-        (R, H, W) uint8 (device tensors): per region the first arg-max of `instances.scores` and that query's mask."""
+        (R, H, W) uint8 (device tensors): per region the first arg-max of `instances.scores` and that query's mask -- and, with the model's
+        `mask_boxes` switch on, `picked_boxes` (R, 4) float32 / `picked_areas` (R) int32 of those masks."""
         self._session_mode_check()
         if not isinstance(session, ImageSession) or session.model is not self:
             raise ValueError("segment: this session was made by another model (or replica)")
@@ -2249,9 +2264,31 @@ class PSALM:
         With `c_stages` (default) the dozen launches are ONE native call, psalm_postprocess_<task> (csrc/stages.hip: the same op-level entries in
         the same order -- `_post_tail_ops` is that sequence issued from Python, kept as the test's reference and for the cases the native entry
         leaves out: bf16 / exact-fp32 class maps, vocabularies above 160 classes)."""
-        if self._post_native_ok(h):
-            return self._post_tail_native(h, sizes)
-        return self._post_tail_ops(h, sizes)
+        res = self._post_tail_native(h, sizes) if self._post_native_ok(h) else self._post_tail_ops(h, sizes)
+        if self.mask_boxes and res["_pending"][0] != "semantic":
+            self._post_boxes(res)
+        return res
+
+    _PEND_MASKS_BOXES = {"instance": (5, 6), "panoptic": (5, 7), "referring": (3, 4), "region": (2, 3)}
+
+    def _post_boxes(self, res):
+        """`mask_boxes` switch: the boxes of the formed instance masks into the `boxes` buffer that held the zeros, their areas beside it
+        (`_finalize` slices both); panoptic: the [x0, y0, x1, y1, area] table of the id map into the tail of the `counts` block, so that it
+        arrives with the image's one host round trip.  Rows past the instance count describe rows of `inst_masks` nobody wrote: sliced off."""
+        o, pend = self.ops, res["_pending"]
+        im, ib = self._PEND_MASKS_BOXES[pend[0]]
+        _, res["_areas"] = o.mask_boxes(pend[im], out_boxes=pend[ib])
+        if pend[0] == "panoptic":
+            Q = self.cfg.md_queries
+            o.label_boxes(pend[6], Q + 1, out=pend[4][2 + 3 * Q:].view(Q + 1, 5))       # segment ids are 1 .. segments <= Q; 0 = void
+
+    def _counts_extra(self):
+        """int32 words behind the panoptic `counts` block for the segment table of `_post_boxes`"""
+        if not (self.mask_boxes and self.seg_task == "panoptic"):
+            return 0
+        if self.cfg.md_queries + 1 > 256:
+            raise NotImplementedError("mask_boxes: panoptic segment boxes for at most 255 queries (psalm_label_boxes: n_ids <= 256)")
+        return 5 * (self.cfg.md_queries + 1)
 
     def _post_native_ok(self, h):
         if not (self.c_stages and self.precision in ("f16x3", "fp32") and self.cfg.md_queries <= 128 and getattr(self.ops.lib, "records", None) is None
@@ -2270,7 +2307,7 @@ class PSALM:
                             seg_logits=r["pred_SEG_logits"] if task == "referring" else None,
                             region_logits=r["pred_region_logits"] if task == "region" else None,
                             is_thing=self._thing_dev(C1 - 1) if task == "panoptic" else None,
-                            obj_thr=cfg.object_mask_threshold, overlap_thr=cfg.overlap_threshold)
+                            obj_thr=cfg.object_mask_threshold, overlap_thr=cfg.overlap_threshold, counts_extra=self._counts_extra())
         res = {"_hw": (height, width), "_crop": (oh, ow), "mask_pred": out["mask_pred"]}
         if task == "semantic":
             res["sem_seg"] = out["sem_seg"]
@@ -2322,11 +2359,12 @@ class PSALM:
             sem, mscore = self._semantic(mflat, probsT, h["Kpad"], want_mask_score=True)                     # LP:402-406, 443-444
             res["sem_seg"] = sem.view(C1 - 1, height, width)
             thing = self._thing_dev(C1 - 1)
-            counts = o.zeros(2 + 3 * Q, dtype=torch.int32)      # [instances kept, segments, segments_info (Q,3)]: ONE device-to-host copy
+            # [instances kept, segments, segments_info (Q,3)] (+ the segment table of `_post_boxes`): ONE device-to-host copy
+            counts = o.zeros(2 + 3 * Q + self._counts_extra(), dtype=torch.int32)
             sc, cl, qq, cnt = o.topk_select(probs, C1 - 1, Q, thing, mscore, count_out=counts[0:1])          # LP:407-447
             inst_masks = o.binarize_gather(mp, Q, qq, cnt)
             pan, pinfo, ninfo = o.panoptic(mp, score, label, thing, C1 - 1, cfg.object_mask_threshold, cfg.overlap_threshold,
-                                           info_out=counts[2:].view(Q, 3), ninfo_out=counts[1:2])
+                                           info_out=counts[2:2 + 3 * Q].view(Q, 3), ninfo_out=counts[1:2])
             # (LongTensor labels / indices and the all-zero pred_boxes of `Instances` are made HERE, by this library's cast / memset:
             #  _finalize only slices -- no framework kernel per image)
             res["_pending"] = ("panoptic", sc, o.to_i64(cl), o.to_i64(qq), counts, inst_masks, pan, o.zeros(sc.shape[0], 4))
@@ -2364,12 +2402,15 @@ class PSALM:
         pend = res.pop("_pending")
         hw = res.pop("_hw")
         oh, ow = res.pop("_crop")
+        areas = res.pop("_areas", None)                            # (`mask_boxes` switch on: see _post_boxes)
         if pend[0] == "semantic":
             return res
         if pend[0] == "instance":
             _, sc, cl, qq, cnt, inst_masks, boxes = pend
             n = int(cnt.item())
             res["instances"] = Instances(hw, pred_masks=inst_masks[:n], scores=sc[:n], pred_classes=cl[:n], query_index=qq[:n], pred_boxes=boxes[:n])
+            if areas is not None:
+                res["instances"].set("pred_areas", areas[:n])
             return res
         if pend[0] == "panoptic":
             _, sc, cl, qq, counts, inst_masks, pan, boxes = pend
@@ -2377,10 +2418,19 @@ class PSALM:
             n, ni = hc[0], hc[1]
             res["instances"] = Instances(hw, pred_masks=inst_masks[:n], scores=sc[:n], pred_classes=cl[:n], query_index=qq[:n], pred_boxes=boxes[:n])
             rows = [hc[2 + 3 * i: 5 + 3 * i] for i in range(ni)]
-            res["panoptic_seg"] = (pan, [{"id": a, "isthing": bool(b), "category_id": c} for a, b, c in rows])
+            info_rows = [{"id": a, "isthing": bool(b), "category_id": c} for a, b, c in rows]
+            if areas is not None:                                 # COCO panoptic JSON fields: "area", "bbox" = [x, y, w, h]
+                res["instances"].set("pred_areas", areas[:n])
+                tab = 2 + 3 * self.cfg.md_queries
+                for seg in info_rows:
+                    x0, y0, x1, y1, a = hc[tab + 5 * seg["id"]: tab + 5 * seg["id"] + 5]
+                    seg["area"], seg["bbox"] = a, [x0, y0, x1 - x0, y1 - y0]
+            res["panoptic_seg"] = (pan, info_rows)
         elif pend[0] == "referring":
             _, sc, qq, inst_masks, boxes = pend
             res["instances"] = Instances(hw, pred_masks=inst_masks, scores=sc, query_index=qq, pred_boxes=boxes)
+            if areas is not None:
+                res["instances"].set("pred_areas", areas)
         else:
             _, scores, inst_masks, boxes = pend
             gt = getattr(info.get("instances"), "gt_masks", None) if gt_optional else info["instances"].gt_masks
@@ -2389,6 +2439,8 @@ class PSALM:
                 gt = gt.to(self.device, torch.float32).contiguous()
                 res["gt"] = self.ops.resize_planes(gt, hw[0], hw[1], crop=(oh, ow))                          # LP:1458-1461
             res["instances"] = Instances(hw, pred_masks=inst_masks, scores=scores, pred_boxes=boxes)
+            if areas is not None:
+                res["instances"].set("pred_areas", areas)
         return res
 
     # ---- hipGraph execution: the ~600 launches of one call are captured once per input signature and replayed
@@ -2397,7 +2449,8 @@ class PSALM:
         padded image size (itself a function of img_shape); the sequence length and the row-set sizes enter bucketed (`_bucketed`)."""
         return (self.seg_task, self.precision, self.llm_products, meta["video"], meta["img_shape"], meta["L"], meta["n_cls"], meta["n_regions"],
                 meta["post"] if self.graph_tail else len(meta["post"]),
-                meta["layout"], tuple(int(bool(x)) for x in self.is_thing_list) if self.is_thing_list is not None else None)
+                meta["layout"], tuple(int(bool(x)) for x in self.is_thing_list) if self.is_thing_list is not None else None,
+                bool(self.mask_boxes) and self.graph_tail)
 
     def _run_graphed(self, images, blob, layout, meta, vp_images=None):
         key = self._graph_key(meta)

@@ -157,7 +157,10 @@ class VideoTracker:
         else:
             self._mem = _Memory(keep, masks, row_cnt, [int(x) for x in rnz], fill)
             updated = True
-        return {"picked_masks": picked, "fused": fused,
+        extra = {}
+        if getattr(self.model, "mask_boxes", False):        # where each object is: (x0, y0, x1, y1) of its picked mask, zeros when it is empty
+            extra["boxes"] = o.mask_boxes(picked)[0]        # (the areas are the `nonzero` counts the read-back has brought already)
+        return {**extra, "picked_masks": picked, "fused": fused,
                 "picked_query": torch.from_numpy(host[1 + 2 * R:1 + 3 * R].astype(np.int64)),
                 "picked_scores": torch.from_numpy(host[1 + 3 * R:1 + 4 * R].copy().view(np.float32)),
                 "pair_inter": torch.from_numpy(host[1 + 4 * R:1 + 4 * R + R * R].reshape(R, R).copy()),
@@ -174,6 +177,8 @@ class VideoTracker:
 
         Returns what `eval_video` returns for the frame (`instances`, `gt`, `mask_pred`) plus
             picked_masks (R,H,W) uint8, fused (H,W) uint8            on the device, private copies
+            boxes (R,4) float32                                      on the device, only with the model's `mask_boxes` switch on: (x0, y0, x1, y1)
+                                                                     of each picked mask, zeros for an empty one
             picked_query (R) int64, picked_scores (R) float32,
             pair_inter / pair_union (R,R) int32                      on the host (they arrive with the step's one read-back)
             used_memory, memory_updated                              bools.
