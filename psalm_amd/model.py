@@ -44,6 +44,8 @@ import torch
 from . import hip_ops as H
 from .config import (CLS_TOKEN_INDEX, IMAGE_TOKEN_INDEX, REFER_TOKEN_INDEX, REGION_TOKEN_INDEX, SEG_TOKEN_INDEX,
                      PsalmConfig)
+from .session import (ImageSession, SessionMixin, default_region_index_sampler,  # noqa: F401  (the image-session half of PSALM; re-exported)
+                      default_region_point_sampler)
 
 
 class Instances:
@@ -91,27 +93,6 @@ def _nonzero_2d(m: torch.Tensor) -> torch.Tensor:
     return torch.from_numpy(np.stack((flat // W, flat % W), 1))
 
 
-def default_region_point_sampler(nonzero: torch.Tensor, n: int) -> torch.Tensor:
-    """Row indices into `nonzero` (context_cluster.py:31-40 rand_sample_repeat; global torch CPU RNG, same call order)."""
-    m = nonzero.shape[0]
-    if m < n:
-        return torch.cat((torch.arange(m), torch.randint(0, m, (n - m,))))
-    if m == n:
-        return torch.arange(m)
-    return torch.randperm(m)[:n]
-
-
-def default_region_index_sampler(m: int, n: int) -> torch.Tensor:
-    """`default_region_point_sampler` (context_cluster.py:31-40 rand_sample_repeat) with the number of non-zero pixels as its argument: row indices
-    into a `nonzero()` of m rows.  The same global-RNG calls in the same order."""
-    m = int(m)
-    if m < n:
-        return torch.cat((torch.arange(m), torch.randint(0, m, (n - m,))))
-    if m == n:
-        return torch.arange(m)
-    return torch.randperm(m)[:n]
-
-
 class _VisionTower:
     """What `model.get_vision_tower()` hands the reference's builder (psalm/model/builder.py:57-65): `.image_processor` -- the dict
     of the three dataset mappers (llava_phi.py:66-69) -- and a `.to(...)` that the builder calls to move the tower."""
@@ -124,33 +105,7 @@ class _VisionTower:
         return self
 
 
-class ImageSession:
-    """What `PSALM.encode_image` keeps on the device for one image, so that `PSALM.segment` runs only the prompt-dependent part of the model:
-    the four Swin levels (`feats`), the projector's image tokens, the pixel decoder's outputs (`mask_features`, `multi_scale_features` + sizes),
-    the predictor's K / V front per region count (built lazily) and the Phi prefix cache -- RoPE'd K and V of the prompt-independent first P rows
-    (system text + image tokens) of every layer, built on the first `segment` call and reused while the leading text ids stay the same
-    (`prefix_builds` / `prefix_hits` count both).  Belongs to the model (or replica) that made it."""
-
-    def __init__(self, model, images, seg_info, feats, image_tokens, n_img, pd):
-        self.model, self.version = model, model._weights_version
-        self.images, self.seg_info = images, seg_info
-        self.feats, self.image_tokens, self.n_img = feats, image_tokens, n_img
-        self.mask_features, self.multi_scale_features, self.shapes, self.mask_features_size = pd
-        self.kv = {}                              # region count -> predictor K / V handle (session-owned workspace)
-        self.prefix_key = None                    # tuple of the leading text ids the cache below was built for
-        self.prefix_len = 0                       # P
-        self.prefix_cache = None                  # (buffer, per-layer (K (heads, ceil32 P, 64), V (P, hidden)) views)
-        self.prefix_builds = self.prefix_hits = 0
-        self.region_tables = None                 # `regions=` prompts: (geometry, row table, column table) of psalm_mask_resize_nearest_pad on the device
-
-    def nbytes(self) -> int:
-        """device bytes held: vision tensors + K / V fronts + prefix cache (2 * layers * P * hidden * 4 up to padding)"""
-        ts = [t for t, _, _ in self.feats] + [self.image_tokens, self.mask_features] + list(self.multi_scale_features)
-        n = sum(t.numel() * t.element_size() for t in ts) + sum(h[0][0].numel() for h in self.kv.values() if h is not None)
-        return n + (self.prefix_cache[0].numel() if self.prefix_cache is not None else 0)
-
-
-class PSALM:
+class PSALM(SessionMixin):
     # The default is the mode that meets the reference's fp32 results to the north star's tolerance; "bf16" is the faster, looser mode.
     DEFAULT_PRECISION = "f16x3"
 
@@ -897,53 +852,81 @@ class PSALM:
         return (torch.stack(pts) if pts else torch.zeros(0, n, 2)), counts
 
     # ======================================================================================= Phi decoder
-    def llm(self, embeds, key_mask, B, L):
-        """PhiModel.forward (modeling_phi.py:343-396) on inputs_embeds (B*L, hidden) fp32; key_mask (B,L) u8."""
+    def _phi_session_desc(self):
+        """the Phi layers' descriptor of the stage-level native calls (psalm_phi_forward / _prefix / _suffix / _suffix_grouped)"""
+        o, w, cfg = self.ops, self.w, self.cfg
+        key = ("phi_desc",)
+        if key not in self._cache:                # (pointers into the weight arena: built once per model instance / replica)
+            self._cache[key] = o.phi_desc([dict(w1=w[f"llm{i}.w1"], b1=w[f"llm{i}.b1"], w2=w[f"llm{i}.w2"], b2=w[f"llm{i}.b2"],
+                                                ln_g=w[f"llm{i}.ln.g"], ln_b=w[f"llm{i}.ln.b"], bnd=w[f"llm{i}.bnd"],
+                                                paired=self.paired.get(f"llm{i}", False)) for i in range(cfg.num_layers)],
+                                          cfg.hidden_size, cfg.intermediate_size, cfg.num_heads, cfg.head_dim, cfg.rotary_dim, cfg.layer_norm_eps,
+                                          w["llm.final.g"], w["llm.final.b"])
+        return self._cache[key]
+
+    def _llm_setup(self, embeds, key_mask):
+        """What a pass over the Phi layers decides and allocates before layer 0, for `llm` and `_llm_session` alike.  Returns (desc, None) when
+        the pass can be one stage-level native call, else (None, (h, big, a2, inv2)): the first LayerNorm's output, the [k|v|q|fc1] buffer and the
+        split-f16 operand [attn | gelu(fc1)] of the [dense | fc2] GEMM with its row scales (None, None when that hand-over is off)."""
         o, w, cfg = self.ops, self.w, self.cfg
         Hd, I = cfg.hidden_size, cfg.intermediate_size
-        cos, sin = self._rope(L)
-        x = embeds
+        rows = embeds.shape[0]
         # f16x3: gelu(fc1) (GEMM epilogue) and the attention output leave directly as the split-f16 A operand [attn | gelu(fc1)] of the
         # [dense | fc2] GEMM -- one operand buffer, one scale per row from a magnitude bound (psalm_gemm_x3_split)
         fuse_split = self.fuse_split and (Hd + I) % 64 == 0 and Hd % 8 == 0 and "llm0.bnd" in w and cfg.head_dim == 64 and cfg.rotary_dim == 32
         if fuse_split and self.c_stages and self.x3 and getattr(o.lib, "records", None) is None and not (H._DEBUG_BOUNDS or o.debug_bounds) \
                 and key_mask.is_contiguous():
-            key = ("phi_desc",)
-            if key not in self._cache:                # (pointers into the weight arena: built once per model instance / replica)
-                self._cache[key] = o.phi_desc([dict(w1=w[f"llm{i}.w1"], b1=w[f"llm{i}.b1"], w2=w[f"llm{i}.w2"], b2=w[f"llm{i}.b2"],
-                                                    ln_g=w[f"llm{i}.ln.g"], ln_b=w[f"llm{i}.ln.b"], bnd=w[f"llm{i}.bnd"],
-                                                    paired=self.paired.get(f"llm{i}", False)) for i in range(cfg.num_layers)],
-                                              Hd, I, cfg.num_heads, cfg.head_dim, cfg.rotary_dim, cfg.layer_norm_eps, w["llm.final.g"], w["llm.final.b"])
-            if self.llm_products != 3:
-                o.x3_products(self.llm_products)
-            try:
-                return o.phi_forward(self._cache[key], embeds, key_mask, cos, sin, B, L)
-            finally:
-                if self.llm_products != 3:
-                    o.x3_products(3)
-        big = o.empty(B * L, 3 * Hd if fuse_split else 3 * Hd + I, dtype=self.adt)
+            return self._phi_session_desc(), None
+        big = o.empty(rows, 3 * Hd if fuse_split else 3 * Hd + I, dtype=self.adt)
+        a2 = inv2 = None
         if fuse_split:
-            a2 = o.empty(B * L, 2 * (Hd + I), dtype=torch.float16)
-            inv2 = o.empty(B * L, dtype=torch.float32)
-        fused = self.adt == torch.bfloat16           # residual projection + the NEXT layer's LayerNorm in one call (psalm_gemm_ln)
+            a2 = o.empty(rows, 2 * (Hd + I), dtype=torch.float16)
+            inv2 = o.empty(rows, dtype=torch.float32)
         if self.paired.get("llm0", False) and not fuse_split:
             raise H.PsalmHipError("the Phi fc1 rows are laid out for paired split-f16 stores but the fused operand hand-over is off "
                                   "(build the model with paired_split_stores=False)")
         if self.x3:                                  # f16x3: LayerNorm emits the [k|v|q|fc1] GEMM's split-f16 A operand directly
-            h = o.layernorm_split(x, w["llm0.ln.g"], w["llm0.ln.b"], cfg.layer_norm_eps)[1]
+            h = o.layernorm_split(embeds, w["llm0.ln.g"], w["llm0.ln.b"], cfg.layer_norm_eps)[1]
         else:
-            h = o.layernorm(x, w["llm0.ln.g"], w["llm0.ln.b"], cfg.layer_norm_eps, out_dtype=self.adt)
+            h = o.layernorm(embeds, w["llm0.ln.g"], w["llm0.ln.b"], cfg.layer_norm_eps, out_dtype=self.adt)
+        return None, (h, big, a2, inv2)
+
+    def _llm_attend(self, cos, sin, key_mask, B, L):
+        """the attention step of the one-shot pass for `_llm_layers`: causal attention over the B sequences of L rows"""
+        o, cfg = self.ops, self.cfg
+        Hd = cfg.hidden_size
+
+        def attend(i, split, big, *out):
+            (o.causal_attention_split if split else o.causal_attention)(big, 2 * Hd, 0, Hd, *out, cos, sin, key_mask, B, L, cfg.num_heads,
+                                                                       cfg.head_dim, cfg.rotary_dim)
+        return attend
+
+    def llm(self, embeds, key_mask, B, L):
+        """PhiModel.forward (modeling_phi.py:343-396) on inputs_embeds (B*L, hidden) fp32; key_mask (B,L) u8."""
+        o = self.ops
+        cos, sin = self._rope(L)
+        desc, state = self._llm_setup(embeds, key_mask)
         if self.llm_products != 3:
             o.x3_products(self.llm_products)             # thread-local launch-time policy of the split-f16 GEMMs: reset below
         try:
-            return self._llm_layers(x, h, big, a2 if fuse_split else None, inv2 if fuse_split else None, fuse_split, fused, cos, sin, key_mask, B, L)
+            if desc is not None:
+                return o.phi_forward(desc, embeds, key_mask, cos, sin, B, L)
+            # bf16: residual projection + the NEXT layer's LayerNorm in one call (psalm_gemm_ln)
+            return self._llm_layers(embeds, *state, self._llm_attend(cos, sin, key_mask, B, L), fused=self.adt == torch.bfloat16)
         finally:
             if self.llm_products != 3:
                 o.x3_products(3)
 
-    def _llm_layers(self, x, h, big, a2, inv2, fuse_split, fused, cos, sin, key_mask, B, L):
+    def _llm_layers(self, x, h, big, a2, inv2, attend, fused=False):
+        """The Phi layers op by op -- the sequence the stage-level native calls of csrc/stages.hip issue -- behind `_llm_setup`; returns the
+        final-LayerNorm hidden states.  The attention step is the caller's: `attend(i, split, big, *out)` reads layer i's q / k / v at columns
+        2 * hidden / 0 / hidden of `big` and writes its output to `out` -- split = True: (a2, inv2, 0), the split-f16 operand, its row scales and the
+        column offset (the `_split` form of the attention kernel); False: (big, 2 * hidden), over q in place.  Flavours: one-shot (`_llm_attend`),
+        and `_llm_session`'s prefix build, suffix against a cache and suffix against a table of cache references.  A true return value ends the
+        pass there (the prefix build, behind the last layer's K / V): None is returned."""
         o, w, cfg = self.ops, self.w, self.cfg
         Hd, I = cfg.hidden_size, cfg.intermediate_size
+        fuse_split = a2 is not None
         for i in range(cfg.num_layers):
             last = i == cfg.num_layers - 1
             ng, nb = (w["llm.final.g"], w["llm.final.b"]) if last else (w[f"llm{i + 1}.ln.g"], w[f"llm{i + 1}.ln.b"])
@@ -951,8 +934,8 @@ class PSALM:
                 o.gemm_x3_split(h, w[f"llm{i}.w1"], w[f"llm{i}.b1"], H.ACT_GELU_NEW, a2, inv2, w[f"llm{i}.bnd"], split_col_off=Hd,
                                 split_col_start=3 * Hd, act_col_start=3 * Hd, out=big, global_rows=True,
                                 paired=self.paired.get(f"llm{i}", False))
-                o.causal_attention_split(big, 2 * Hd, 0, Hd, a2, inv2, 0, cos, sin, key_mask, B, L, cfg.num_heads, cfg.head_dim,
-                                         cfg.rotary_dim)
+                if attend(i, True, big, a2, inv2, 0):
+                    return None
                 if last or Hd % 64 != 0 or Hd > 2048:
                     x = o.gemm(H.SplitF16(a2, inv2, Hd + I), w[f"llm{i}.w2"], w[f"llm{i}.b2"], residual=x, out_dtype=torch.float32)
                     h = o.layernorm(x, ng, nb, cfg.layer_norm_eps, out_dtype=torch.float32) if last else \
@@ -963,8 +946,8 @@ class PSALM:
                 continue
             o.gemm(h, w[f"llm{i}.w1"], w[f"llm{i}.b1"], act=H.ACT_GELU_NEW, act_col_start=3 * Hd, out=big)
             # columns: [k | v | q | gelu_new(fc1)];  attention output overwrites q in place
-            o.causal_attention(big, 2 * Hd, 0, Hd, big, 2 * Hd, cos, sin, key_mask, B, L, cfg.num_heads, cfg.head_dim,
-                               cfg.rotary_dim)
+            if attend(i, False, big, big, 2 * Hd):
+                return None
             if fused:
                 x, h = o.gemm_ln(big[:, 2 * Hd:], w[f"llm{i}.w2"], w[f"llm{i}.b2"], x, ng, nb, cfg.layer_norm_eps,
                                  ln_dtype=torch.float32 if last else self.adt)
@@ -1288,6 +1271,40 @@ class PSALM:
             self._side = torch.cuda.Stream(device=self.device)
         return self._side
 
+    # ======================================================================================= LLM states -> decoder operands
+    def _decoder_embeddings(self, hidden, dv):
+        """LP:1366-1390: the means of the blob's row sets of `hidden` through their projectors -> (seg_q (prompts * Q, D) fp32, class-name, <refer> and
+        <region> embeddings or None).  (The row-set means come out in the GEMM operand dtype: bf16 -> the skinny MFMA kernel, not the converting path.)"""
+        o, w = self.ops, self.w
+        seg_q = o.gemm(o.segment_mean(hidden, dv["seg_off"], dv["seg_rows"], out_dtype=self.adt), w["seg_query_projector.w"],
+                       w["seg_query_projector.b"], out_dtype=torch.float32)
+        cls_emb = seg_emb = reg_emb = None
+        if "cls_off" in dv:
+            cls_emb = o.gemm(o.segment_mean(hidden, dv["cls_off"], dv["cls_rows"], out_dtype=self.adt), w["class_name_projector.w"],
+                             w["class_name_projector.b"], out_dtype=self.wdt)
+        if "refer_off" in dv:
+            seg_emb = o.gemm(o.segment_mean(hidden, dv["refer_off"], dv["refer_rows"], out_dtype=self.adt), w["SEG_token_projector.w"],
+                             w["SEG_token_projector.b"], out_dtype=self.wdt)
+        if "region_off" in dv:
+            reg_emb = o.gemm(o.segment_mean(hidden, dv["region_off"], dv["region_rows"], out_dtype=self.adt), w["region_projector.w"],
+                             w["region_projector.b"], out_dtype=self.adt)
+        return seg_q, cls_emb, seg_emb, reg_emb
+
+    def _prompt_operands(self, seg_q, cls_emb, seg_emb, reg_emb, n_cls, n_regions):
+        """`_decoder_embeddings`' tensors cut per prompt (image of a batch, prompt of a session): yields `predictor`'s (seg_query, SEG_emb,
+        class_emb, region_emb) -- views; n_cls / n_regions: the class-name and region counts per prompt."""
+        Q = self.cfg.md_queries
+        c0 = r0 = 0
+        for b, nc in enumerate(n_cls):
+            ce = cls_emb[c0:c0 + nc] if cls_emb is not None else None
+            c0 += nc
+            se = seg_emb[b:b + 1] if seg_emb is not None else None
+            re = None
+            if reg_emb is not None:
+                re = reg_emb[r0:r0 + n_regions[b]]
+                r0 += n_regions[b]
+            yield seg_q[b * Q:(b + 1) * Q], se, ce, re
+
     # ======================================================================================= device forward
     def _forward_device(self, images, dv, meta, stages: Optional[dict] = None, postprocess: bool = True, vp_images=None, vp_tokens=None,
                         region_pts=None):
@@ -1337,27 +1354,12 @@ class PSALM:
         if stages is not None:
             Lr = max(meta["lens"])                    # (L is the bucketed length: hand the stage tensors out at the real one)
             stages.update(inputs_embeds=embeds.view(B, L, -1)[:, :Lr], hidden_states=hidden.view(B, L, -1)[:, :Lr], lengths=meta["lens"])
-        # ---- LLM states -> decoder embeddings (LP:1366-1390)
-        Q = cfg.md_queries
-        # (row-set means come out in the GEMM operand dtype: bf16 -> the skinny MFMA kernel instead of the converting path)
-        seg_q = o.gemm(o.segment_mean(hidden, dv["seg_off"], dv["seg_rows"], out_dtype=self.adt), w["seg_query_projector.w"],
-                       w["seg_query_projector.b"], out_dtype=torch.float32)
-        cls_emb = seg_emb = reg_emb = None
-        if "cls_off" in dv:
-            cls_emb = o.gemm(o.segment_mean(hidden, dv["cls_off"], dv["cls_rows"], out_dtype=self.adt), w["class_name_projector.w"],
-                             w["class_name_projector.b"], out_dtype=self.wdt)
-        if "refer_off" in dv:
-            seg_emb = o.gemm(o.segment_mean(hidden, dv["refer_off"], dv["refer_rows"], out_dtype=self.adt), w["SEG_token_projector.w"],
-                             w["SEG_token_projector.b"], out_dtype=self.wdt)
-        if "region_off" in dv:
-            reg_emb = o.gemm(o.segment_mean(hidden, dv["region_off"], dv["region_rows"], out_dtype=self.adt), w["region_projector.w"],
-                             w["region_projector.b"], out_dtype=self.adt)
+        seg_q, cls_emb, seg_emb, reg_emb = self._decoder_embeddings(hidden, dv)
         if stages is not None:
-            stages.update(seg_query=seg_q.view(B, Q, -1), class_name_embedding=cls_emb, SEG_embedding=seg_emb,
+            stages.update(seg_query=seg_q.view(B, cfg.md_queries, -1), class_name_embedding=cls_emb, SEG_embedding=seg_emb,
                           region_embedding=reg_emb)
         # ---- per image: pixel decoder + predictor (+ post-processing)
         outs = []
-        c0 = r0 = 0
         if side is not None:
             torch.cuda.current_stream().wait_stream(side)
             if not torch.cuda.is_current_stream_capturing():
@@ -1369,21 +1371,13 @@ class PSALM:
                         for t in [po[0]] + list(po[1]) + ([po[4][0][0]] if len(po) > 4 and po[4] is not None else []):
                             if torch.is_tensor(t):
                                 t.record_stream(torch.cuda.current_stream())
-        for b in range(B):
+        for b, prompt in enumerate(self._prompt_operands(seg_q, cls_emb, seg_emb, reg_emb, meta["n_cls"], n_regions)):
             if pd_out[b] is None:
                 pd_out[b] = self.pixel_decoder([(tok[b * h * w_:(b + 1) * h * w_], h, w_) for tok, h, w_ in feats])
                 mf_, ms_, shapes_, mfs_ = pd_out[b]
                 pd_out[b] = pd_out[b] + (self.predictor_kv(ms_, shapes_, mf_, mfs_, n_regions[b] if n_regions else 0, slot=b),)
             mf, ms, shapes, mf_size, kv = pd_out[b]
-            nc = meta["n_cls"][b]
-            ce = cls_emb[c0:c0 + nc] if cls_emb is not None else None
-            c0 += nc
-            se = seg_emb[b:b + 1] if seg_emb is not None else None
-            re = None
-            if reg_emb is not None:
-                re = reg_emb[r0:r0 + n_regions[b]]
-                r0 += n_regions[b]
-            r = self.predictor(ms, shapes, mf, mf_size, seg_q[b * Q:(b + 1) * Q], se, ce, re, kv=kv)
+            r = self.predictor(ms, shapes, mf, mf_size, *prompt, kv=kv)
             if stages is not None:
                 stages.setdefault("mask_features", []).append(mf)
                 stages.setdefault("multi_scale_features", []).append(ms)
@@ -1408,46 +1402,7 @@ class PSALM:
         dv = self._views(torch.from_numpy(blob).to(self.device), layout)
         return self._forward_device(images, dv, meta, stages=stages, postprocess=False, vp_images=vp_images)
 
-    # ======================================================================================= image sessions: encode once, segment many prompts
-    def _session_mode_check(self):
-        if self.precision == "bf16":
-            raise NotImplementedError("image sessions: precision 'bf16' is a side line with its own attention kernels (f16x3 / fp32 only)")
-        if self.llm_products != 3:
-            raise NotImplementedError("image sessions: llm_products=1 is a side mode of the one-shot path (llm_products=3 only)")
-
-    @torch.no_grad()
-    def encode_image(self, images, seg_info=None) -> "ImageSession":
-        """Everything of eval_seg that does not read the prompt, for ONE image ((1, 3, H, W) or (3, H, W), pre-processed as for eval_seg; `seg_info`: its
-        geometry entry -- a dict, or a list holding it): Swin, projector, pixel decoder.  Returns the ImageSession `segment` takes."""
-        self._session_mode_check()
-        if images.dim() == 3:
-            images = images[None]
-        if images.dim() != 4 or images.shape[0] != 1:
-            raise ValueError("encode_image: one image, (1, 3, H, W) or (3, H, W)")
-        if isinstance(seg_info, (list, tuple)):
-            if len(seg_info) != 1:
-                raise ValueError("encode_image: seg_info of one image")
-            seg_info = seg_info[0]
-        images = images.to(self.device, torch.float32).contiguous()
-        feats = self.swin(images)
-        res5, h5, w5 = feats[3]
-        img_tok, n_img = self.projector(res5, 1, h5, w5)
-        pd = self.pixel_decoder([(tok, h, w_) for tok, h, w_ in feats])
-        return ImageSession(self, images, seg_info, feats, img_tok, n_img, pd)
-
-    def _session_kv(self, session, n_reg):
-        """the predictor's K / V front for this region count, in a workspace the session owns (built on first use)"""
-        if n_reg not in session.kv:
-            mf, ms, shapes, mfs = session.mask_features, session.multi_scale_features, session.shapes, session.mask_features_size
-            kv = None
-            if self.kv_side and self._predictor_native_ok(mf):
-                desc, prpos = self._predictor_desc(shapes)
-                cont = lambda t: t if t.is_contiguous() else t.contiguous()       # noqa: E731
-                ms_c, mf_c = [cont(t) for t in ms], cont(mf)
-                kv = (self.ops.predictor_kv(desc, ms_c, shapes, prpos, mf_c, mfs, n_reg, slot=0, own=True), ms_c, mf_c)
-            session.kv[n_reg] = kv
-        return session.kv[n_reg]
-
+    # ---- shared by _prepare and the image-session pipeline (psalm_amd/session.py)
     @staticmethod
     def _pack(arrays):
         """the host arrays of one call as ONE byte blob (one host-to-device copy) + its layout: name -> (offset, elements, dtype)"""
@@ -1463,178 +1418,6 @@ class PSALM:
             blob[o0:o0 + a.nbytes] = a.view(np.uint8).reshape(-1)
         return blob, layout
 
-    def _session_plan(self, session, input_ids, attention_mask, class_name_ids, cls_indices, token_refer_id, n_regions, want_cls, want_refer):
-        """The splice plan of N prompts on the session's image, cut at P = the row just past the last image row: the shared prefix's (sid, srow) and
-        its key (the leading text ids), and the suffix plan -- (N, S) arrays with S bucketed by `len_bucket` as `_bucketed` does for L, row sets
-        re-based from absolute to suffix positions."""
-        ids = input_ids.cpu().numpy().astype(np.int64)
-        N, T = ids.shape
-        n_img = session.n_img
-        t_img = []
-        for b in range(N):
-            pos = np.flatnonzero(ids[b] == IMAGE_TOKEN_INDEX)
-            if pos.shape[0] != 1:
-                raise ValueError(f"segment: prompt {b} holds {pos.shape[0]} <image> tokens, a session prompt has exactly one")
-            if (ids[b, :pos[0]] < 0).any():
-                raise ValueError(f"segment: prompt {b} has a special token at position {int(np.flatnonzero(ids[b, :pos[0]] < 0)[0])}, before <image>: "
-                                 "the shared prefix is text + <image>")
-            t_img.append(int(pos[0]))
-        for b in range(1, N):
-            n = min(t_img[0], t_img[b]) + 1
-            diff = np.flatnonzero(ids[b, :n] != ids[0, :n])
-            if diff.shape[0] or t_img[b] != t_img[0]:
-                at = int(diff[0]) if diff.shape[0] else n
-                raise ValueError(f"segment: prompt {b} differs from prompt 0 at token position {at}; all prompts of a call must share the rows up to "
-                                 "and including <image>")
-        key = tuple(int(v) for v in ids[0, :t_img[0]])
-        P = t_img[0] + n_img
-        plan = self._splice_plan(input_ids, attention_mask, n_img, class_name_ids, cls_indices, token_refer_id, n_regions, want_cls, want_refer)
-        L = plan["L"]
-        if not plan["kmask"][:, :P].all():
-            raise ValueError("segment: the attention mask hides a row of the shared prefix (prefix rows are always real)")
-        S = L - P
-        if S < 1:
-            raise ValueError("segment: nothing follows <image>")
-        q = max(int(self.len_bucket or 0), 1)
-        Sb = (S + q - 1) // q * q
-        sid = np.full((N, Sb), -1, np.int32)
-        srow = np.zeros((N, Sb), np.int32)
-        kmask = np.zeros((N, Sb), np.uint8)
-        sid[:, :S], srow[:, :S], kmask[:, :S] = plan["sid"][:, P:], plan["srow"][:, P:], plan["kmask"][:, P:]
-        psrow = plan["srow"][0, :P].copy()
-        psrow[plan["sid"][0, :P] == 1] %= n_img                   # (one image: its tokens are rows 0 .. n_img-1 whatever the prompt index)
-        out = {"P": P, "S": Sb, "S_real": S, "lens": [l_ - P for l_ in plan["lens"]], "key": key, "n_cls": plan["n_cls"],
-               "prefix": (plan["sid"][0, :P].copy(), psrow), "sid": sid, "srow": srow, "kmask": kmask}
-        for name in ("seg", "cls", "refer", "region"):
-            if plan[name] is None:
-                out[name] = None
-                continue
-            off, rows = plan[name]
-            r64 = rows.astype(np.int64)
-            assert (r64 % L >= P).all(), "row sets live behind the prefix"
-            rows = (r64 // L * Sb + r64 % L - P).astype(np.int32)
-            if name != "seg" and q > 1:
-                n = (rows.shape[0] + q - 1) // q * q
-                rows = np.concatenate((rows, np.zeros(max(n, q) - rows.shape[0], np.int32)))
-            out[name] = (off, rows)
-        return out
-
-    def _phi_session_desc(self):
-        o, w, cfg = self.ops, self.w, self.cfg
-        key = ("phi_desc",)
-        if key not in self._cache:                # (the descriptor PSALM.llm builds: shared)
-            self._cache[key] = o.phi_desc([dict(w1=w[f"llm{i}.w1"], b1=w[f"llm{i}.b1"], w2=w[f"llm{i}.w2"], b2=w[f"llm{i}.b2"],
-                                                ln_g=w[f"llm{i}.ln.g"], ln_b=w[f"llm{i}.ln.b"], bnd=w[f"llm{i}.bnd"],
-                                                paired=self.paired.get(f"llm{i}", False)) for i in range(cfg.num_layers)],
-                                          cfg.hidden_size, cfg.intermediate_size, cfg.num_heads, cfg.head_dim, cfg.rotary_dim, cfg.layer_norm_eps,
-                                          w["llm.final.g"], w["llm.final.b"])
-        return self._cache[key]
-
-    def _llm_session(self, embeds, key_mask, B, L, P, cache, suffix: bool, refs=None):
-        """PSALM.llm cut behind the prompt-independent prefix.  suffix = False: the P prefix rows (B = 1, L = P), every layer's RoPE'd K and its V go
-        into `cache` (Ops.phi_prefix_cache), the last layer stops behind its [k|v|q|fc1] GEMM; returns None.  suffix = True: the B * L suffix rows
-        at positions P .., attention through the prefix kernel against `cache`; returns the final-LayerNorm hidden states (B*L, hidden).
-        One native call each (psalm_phi_prefix / psalm_phi_suffix) under the conditions of PSALM.llm's stage-level call, else this op-by-op
-        sequence -- same launches, same bits (tests/test_11_session_emu.py).
-        refs (suffix only; `segment_many`): (device bytes, host array) of the (num_layers, B) psalm_prefix_ref table -- prompt b attends the cache and
-        prefix length its entries name, P is the largest of them and `cache` is not read; attention through the grouped prefix kernel
-        (psalm_phi_suffix_grouped, or the grouped ops in the same op-by-op sequence).  Off by default: the ungrouped path is untouched."""
-        o, w, cfg = self.ops, self.w, self.cfg
-        Hd, I = cfg.hidden_size, cfg.intermediate_size
-        if cfg.head_dim != 64 or cfg.rotary_dim != 32:
-            raise NotImplementedError("image sessions: the prefix attention kernel is built for head_dim 64 / rotary dim 32 (Phi-1.5)")
-        cos, sin = self._rope(P + L if suffix else P)
-        buf, views = cache if refs is None else (None, None)
-        if refs is not None:
-            assert suffix, "a prefix pass writes one cache"
-            rdev, rhost = refs
-        nh, hd, rd = cfg.num_heads, cfg.head_dim, cfg.rotary_dim
-        fuse_split = self.fuse_split and (Hd + I) % 64 == 0 and Hd % 8 == 0 and "llm0.bnd" in w
-        if fuse_split and self.c_stages and self.x3 and getattr(o.lib, "records", None) is None and not (H._DEBUG_BOUNDS or o.debug_bounds) \
-                and key_mask.is_contiguous():
-            desc = self._phi_session_desc()
-            if refs is not None:
-                return o.phi_suffix_grouped(desc, embeds, key_mask, cos, sin, B, L, rdev, P, table=rhost)
-            if suffix:
-                return o.phi_suffix(desc, embeds, key_mask, cos, sin, B, L, P, buf)
-            o.phi_prefix(desc, embeds, key_mask, cos, sin, P, buf)
-            return None
-        x = embeds
-        big = o.empty(B * L, 3 * Hd if fuse_split else 3 * Hd + I, dtype=torch.float32)
-        if fuse_split:
-            a2 = o.empty(B * L, 2 * (Hd + I), dtype=torch.float16)
-            inv2 = o.empty(B * L, dtype=torch.float32)
-        if self.paired.get("llm0", False) and not fuse_split:
-            raise H.PsalmHipError("the Phi fc1 rows are laid out for paired split-f16 stores but the fused operand hand-over is off "
-                                  "(build the model with paired_split_stores=False)")
-        if self.x3:
-            h = o.layernorm_split(x, w["llm0.ln.g"], w["llm0.ln.b"], cfg.layer_norm_eps)[1]
-        else:
-            h = o.layernorm(x, w["llm0.ln.g"], w["llm0.ln.b"], cfg.layer_norm_eps, out_dtype=self.adt)
-        for i in range(cfg.num_layers):
-            last = i == cfg.num_layers - 1
-            ng, nb = (w["llm.final.g"], w["llm.final.b"]) if last else (w[f"llm{i + 1}.ln.g"], w[f"llm{i + 1}.ln.b"])
-            if refs is None:
-                kc, vc = views[i]
-            else:
-                ri, rh = rdev[32 * B * i:32 * B * (i + 1)], rhost[i]
-            if fuse_split:
-                o.gemm_x3_split(h, w[f"llm{i}.w1"], w[f"llm{i}.b1"], H.ACT_GELU_NEW, a2, inv2, w[f"llm{i}.bnd"], split_col_off=Hd,
-                                split_col_start=3 * Hd, act_col_start=3 * Hd, out=big, global_rows=True, paired=self.paired.get(f"llm{i}", False))
-                if refs is not None:
-                    o.causal_attention_prefix_grouped_split(big, 2 * Hd, 0, Hd, ri, a2, inv2, 0, cos, sin, key_mask, B, L, P, nh, hd, rd, table=rh)
-                elif suffix:
-                    o.causal_attention_prefix_split(big, 2 * Hd, 0, Hd, kc, vc, a2, inv2, 0, cos, sin, key_mask, B, L, P, nh, hd, rd)
-                else:
-                    o.phi_prefix_kv_store(big, 0, Hd, cos, sin, kc, vc, P, nh, hd, rd)
-                    if last:
-                        break
-                    o.causal_attention_split(big, 2 * Hd, 0, Hd, a2, inv2, 0, cos, sin, key_mask, B, L, nh, hd, rd)
-                if last or Hd % 64 != 0 or Hd > 2048:
-                    x = o.gemm(H.SplitF16(a2, inv2, Hd + I), w[f"llm{i}.w2"], w[f"llm{i}.b2"], residual=x, out_dtype=torch.float32)
-                    h = o.layernorm(x, ng, nb, cfg.layer_norm_eps, out_dtype=torch.float32) if last else \
-                        o.layernorm_split(x, ng, nb, cfg.layer_norm_eps)[1]
-                else:
-                    x, h, _ = o.gemm_x3_ln_split(H.SplitF16(a2, inv2, Hd + I), w[f"llm{i}.w2"], w[f"llm{i}.b2"], x, ng, nb, cfg.layer_norm_eps)
-                continue
-            o.gemm(h, w[f"llm{i}.w1"], w[f"llm{i}.b1"], act=H.ACT_GELU_NEW, act_col_start=3 * Hd, out=big)
-            # columns: [k | v | q | gelu_new(fc1)];  attention output overwrites q in place (q was copied out by the RoPE pre-pass)
-            if refs is not None:
-                o.causal_attention_prefix_grouped(big, 2 * Hd, 0, Hd, ri, big, 2 * Hd, cos, sin, key_mask, B, L, P, nh, hd, rd, table=rh)
-            elif suffix:
-                o.causal_attention_prefix(big, 2 * Hd, 0, Hd, kc, vc, big, 2 * Hd, cos, sin, key_mask, B, L, P, nh, hd, rd)
-            else:
-                o.phi_prefix_kv_store(big, 0, Hd, cos, sin, kc, vc, P, nh, hd, rd)
-                if last:
-                    break
-                o.causal_attention(big, 2 * Hd, 0, Hd, big, 2 * Hd, cos, sin, key_mask, B, L, nh, hd, rd)
-            x = o.gemm(big[:, 2 * Hd:], w[f"llm{i}.w2"], w[f"llm{i}.b2"], residual=x, out_dtype=torch.float32)
-            if self.x3 and not last:
-                h = o.layernorm_split(x, ng, nb, cfg.layer_norm_eps)[1]
-            else:
-                h = o.layernorm(x, ng, nb, cfg.layer_norm_eps, out_dtype=torch.float32)
-        return h if suffix else None
-
-    def _session_prefix(self, session, sp):
-        """the session's Phi prefix cache for this call's leading text ids: reused when the key matches, (re)built otherwise"""
-        o, w, cfg = self.ops, self.w, self.cfg
-        if session.prefix_cache is not None and session.prefix_key == sp["key"] and session.prefix_len == sp["P"]:
-            session.prefix_hits += 1
-            return session.prefix_cache
-        P = sp["P"]
-        psid, psrow = sp["prefix"]
-        cache = session.prefix_cache
-        session.prefix_key = None                 # (the buffer is rebuilt in place: not a hit for the old text if the pass below raises midway)
-        if cache is None or session.prefix_len != P:
-            cache = o.phi_prefix_cache(cfg.hidden_size, cfg.num_heads, P, cfg.num_layers)
-        embeds = o.gather_rows([w["embed"], session.image_tokens, w["seg_query"], None], self._dev_i32(psid), self._dev_i32(psrow), cfg.hidden_size,
-                               out_dtype=torch.float32)
-        ones = torch.ones(1, P, dtype=torch.uint8, device=self.device)
-        self._llm_session(embeds, ones, 1, P, P, cache, suffix=False)
-        session.prefix_cache, session.prefix_key, session.prefix_len = cache, sp["key"], P
-        session.prefix_builds += 1
-        return cache
-
     @staticmethod
     def _post_sizes(Hi, Wi, info, div):
         """the post-processing geometry of one image: padded size, extent of the un-padded box, original size"""
@@ -1647,592 +1430,6 @@ class PSALM:
             rows, cols = np.flatnonzero(valid.any(1)), np.flatnonzero(valid.any(0))
             oh, ow = int(rows[-1] - rows[0] + 1), int(cols[-1] - cols[0] + 1)
         return (Hpad, Wpad, oh, ow, int(info.get("height", Hi)), int(info.get("width", Wi)))
-
-    # The mask decoder over the prompts of a session: one native pass over B * Q query rows against the session's one K / V front
-    # (psalm_predictor_forward_batched) in place of B `predictor` calls.  Each prompt's words are those of its own call, so the switch changes time only.
-    batch_decoder = True
-    decoder_batch_max = 8            # prompts per pass: scratch + outputs hold ~2 * B * Q * H2*W2 * 4 bytes of mask logits (1024^2: ~52 MB per prompt)
-
-    def _decode_batched(self, session, prompts):
-        """`predictor`'s result dicts for the prompts of ONE session -- prompts: a list of (seg_query (Q, D), SEG_emb, class_emb, region_emb) as the
-        per-prompt loop passes them -- through the batched decoder, in chunks of `decoder_batch_max`; None when the per-prompt loop must run: fewer
-        than two prompts, `batch_decoder` off, or a prompt outside the native per-prompt path's conditions."""
-        o, cfg = self.ops, self.cfg
-        n = len(prompts)
-        step = int(self.decoder_batch_max)
-        if n < 2 or not self.batch_decoder or step < 2:
-            return None
-        mf, shapes, mfs = session.mask_features, session.shapes, session.mask_features_size
-        if not self._predictor_native_ok(mf):
-            return None
-        Q, D = cfg.md_queries, cfg.md_hidden
-        for sq, se, ce, re in prompts:
-            if sq.dtype != torch.float32 or sq.data_ptr() % 16 or not sq.is_contiguous():
-                return None
-            if any(e is not None and (e.dtype != torch.float32 or e.data_ptr() % 16 or not e.is_contiguous()) for e in (se, ce, re)):
-                return None
-            if (re is not None and re.shape[0] > 192) or any(e is not None and e.shape[0] > 8192 for e in (se, ce)):
-                return None                                       # (outside the exact-fp32 skinny kernel's range: the per-prompt call takes another kernel)
-        kinds = [tuple(e is not None for e in p[1:]) for p in prompts]
-        if len(set(kinds)) != 1:
-            return None
-        kv = self._session_kv(session, int(prompts[0][3].shape[0]) if prompts[0][3] is not None else 0)
-        if kv is None:
-            return None
-        handle, _, mf_c = kv
-        desc, _ = self._predictor_desc(shapes)
-        H2, W2 = mfs
-
-        def rows(pieces):                                         # consecutive slices of one tensor stay a view; others are packed by stream copies
-            if all(a.data_ptr() + a.numel() * 4 == b_.data_ptr() and a.untyped_storage().data_ptr() == b_.untyped_storage().data_ptr()
-                   for a, b_ in zip(pieces, pieces[1:])):
-                return pieces[0].as_strided((sum(int(t.shape[0]) for t in pieces), D), (D, 1))
-            out = o.empty(sum(int(t.shape[0]) for t in pieces), D)
-            r0 = 0
-            for t in pieces:
-                if t.shape[0]:
-                    o.copy_(out[r0:r0 + t.shape[0]], t)
-                r0 += int(t.shape[0])
-            return out
-
-        def own(t):                                               # a prompt's block of the packed logits, 16-byte aligned as a per-prompt call's tensor is
-            if t.data_ptr() % 16 == 0:
-                return t
-            return o.copy_(o.empty(*t.shape), t)
-
-        outs = []
-        for c0 in range(0, n, step):
-            chunk = prompts[c0:c0 + step]
-            B = len(chunk)
-            if B == 1:                                            # (a trailing chunk of one prompt: the per-prompt call, the same words)
-                sq, se, ce, re = chunk[0]
-                outs.append(self.predictor(session.multi_scale_features, shapes, mf, mfs, sq, se, ce, re,
-                                           kv=self._session_kv(session, int(re.shape[0]) if re is not None else 0)))
-                continue
-            has_s, has_c, has_r = kinds[0]
-            cnt = lambda k: [int(p[k].shape[0]) for p in chunk]  # noqa: E731
-            masks, cls_l, seg_l, reg_l = o.predictor_forward_batched(
-                desc, shapes, handle, mf_c, mfs, rows([p[0] for p in chunk]),
-                class_emb=rows([p[2] for p in chunk]) if has_c else None, cls_counts=cnt(2) if has_c else None,
-                seg_emb=rows([p[1] for p in chunk]) if has_s else None, seg_counts=cnt(1) if has_s else None,
-                region_emb=rows([p[3] for p in chunk]) if has_r else None, reg_counts=cnt(3) if has_r else None)
-            oc = os_ = or_ = 0
-            for b, (sq, se, ce, re) in enumerate(chunk):
-                r = {"pred_masks": masks[b * Q:(b + 1) * Q].view(Q, H2, W2), "pred_class_name_logits": None, "pred_SEG_logits": None,
-                     "pred_region_logits": None}
-                if has_c:
-                    k = int(ce.shape[0])
-                    r["pred_class_name_logits"] = own(cls_l[Q * oc:Q * (oc + k)].view(Q, k))
-                    oc += k
-                if has_s:
-                    k = int(se.shape[0])
-                    r["pred_SEG_logits"] = own(seg_l[Q * os_:Q * (os_ + k)].view(Q, k))
-                    os_ += k
-                if has_r:
-                    k = int(re.shape[0])
-                    r["pred_region_logits"] = own(reg_l[Q * or_:Q * (or_ + k)].view(k, Q))
-                    or_ += k
-                outs.append(r)
-        return outs
-
-    # ---- region prompts given as geometry (`regions=` of segment / segment_many): the dataset mapper's host preparation of a click -- draw the prompt,
-    # enhance_with_circles, apply_segmentation, nonzero() (coco_instance_mapper.py:233-252, context_cluster.py:345-356) -- on the device.  The host
-    # validates and packs a primitive table; psalm_mask_rasterize / psalm_mask_dilate_disc / psalm_mask_resize_nearest_pad make the (S, S) region masks
-    # the host path would have uploaded; ONE read-back brings the R pixel totals the sampler needs; psalm_mask_select_points turns its ranks into the
-    # points `region_points` would have computed, bit for bit.
-    REGION_PROMPT_KEYS = ("points", "scribble", "box", "mask", "rle")
-    REGION_PROMPT_RADIUS = {"points": 10, "scribble": 5}              # coco_instance_mapper.py:247-250
-    REGION_PROMPT_MAX_RADIUS = 16
-
-    def _region_prompt_plan(self, session, input_ids, seg_info, regions, tag="", transforms=None, canvas=None):
-        """Host side of `regions=` for the N prompts of one session: validation (ValueError naming prompt and region) and the arrays that travel in
-        the call's blob under names ending in `tag` -- the primitive table (n, 6) int32, the radii (R) int32 (-1: not dilated), host mask prompts,
-        the all-zero image index of region_pool.  R = all regions of the N prompts, prompt by prompt.  Without a session (`session=None`, the
-        video tracker): the image's geometry as `transforms` (its resize / pad record) and `canvas` (the (H, W) of the model's input)."""
-        from .preprocess import rle_to_mask
-        if self.seg_task != "region":
-            raise ValueError(f"regions are prompts of the region task (this model's seg_task = {self.seg_task!r})")
-        if session is not None:
-            transforms = session.seg_info.get("transforms") if isinstance(session.seg_info, dict) else None
-            canvas = (session.images.shape[2], session.images.shape[3])
-        tr, whose = transforms, "session" if session is not None else "frame"
-        if tr is None:
-            raise ValueError("regions need the session's seg_info['transforms'] (the resize / pad record of the image: encode_image(images, seg_info))")
-        h, w, nh, nw = [int(v) for v in tr["resize"]]
-        ph, pw = [int(v) for v in tr["pad"]]
-        Hi, Wi = int(canvas[0]), int(canvas[1])
-        if (nh + ph, nw + pw) != (Hi, Wi):
-            raise ValueError(f"the {whose}'s transforms lead to {(nh + ph, nw + pw)}, its image is {(Hi, Wi)}")
-        N = int(input_ids.shape[0])
-        if not isinstance(regions, (list, tuple)) or len(regions) != N:
-            raise ValueError(f"regions: one list of region prompts per prompt ({N} prompts)")
-        n_tok = (input_ids == REGION_TOKEN_INDEX).sum(1).tolist()
-        prims, radii, masks, counts = [], [], [], []
-
-        def coord(v, what, where):
-            if isinstance(v, (bool, np.bool_)) or not isinstance(v, (int, np.integer)):
-                raise ValueError(f"{where}: {what} {v!r} is not an integer pixel coordinate")
-            return int(v)
-
-        for b, entry in enumerate(regions):
-            if not isinstance(entry, (list, tuple)) or len(entry) != n_tok[b]:
-                got = len(entry) if isinstance(entry, (list, tuple)) else type(entry).__name__
-                raise ValueError(f"prompt {b}: {got} region prompts for {n_tok[b]} <region> tokens")
-            inst = seg_info[b].get("instances") if isinstance(seg_info[b], dict) else None
-            if getattr(inst, "region_masks", None) is not None:
-                raise ValueError(f"prompt {b}: regions given together with seg_info's instances.region_masks")
-            counts.append(len(entry))
-            for j, rp in enumerate(entry):
-                where = f"prompt {b}, region {j}"
-                g = len(radii)
-                kinds = [k for k in self.REGION_PROMPT_KEYS if isinstance(rp, dict) and k in rp]
-                if len(kinds) != 1:
-                    raise ValueError(f"{where}: a region prompt is a dict with exactly one of {self.REGION_PROMPT_KEYS}, got "
-                                     f"{sorted(rp) if isinstance(rp, dict) else type(rp).__name__}")
-                kind = kinds[0]
-                extra = sorted(set(rp) - {kind} - ({"radius"} if kind in self.REGION_PROMPT_RADIUS else set()))
-                if extra:
-                    raise ValueError(f"{where}: unknown keys {extra} in a {kind!r} prompt")
-                if kind in self.REGION_PROMPT_RADIUS:
-                    rad = rp.get("radius", self.REGION_PROMPT_RADIUS[kind])
-                    if isinstance(rad, (bool, np.bool_)) or not isinstance(rad, (int, np.integer)) or not 0 <= int(rad) <= self.REGION_PROMPT_MAX_RADIUS:
-                        raise ValueError(f"{where}: radius {rad!r} outside 0..{self.REGION_PROMPT_MAX_RADIUS}")
-                    pix = list(rp[kind])
-                    if not pix:
-                        raise ValueError(f"{where}: an empty {kind!r} list")
-                    for p in pix:
-                        if len(p) != 2:
-                            raise ValueError(f"{where}: {p!r} is not a (y, x) pair")
-                        y, x = coord(p[0], "y", where), coord(p[1], "x", where)
-                        if not (0 <= y < h and 0 <= x < w):
-                            raise ValueError(f"{where}: pixel {(y, x)} outside the image of {(h, w)}")
-                        prims.append((g, 0, y, x, 0, 0))
-                    radii.append(int(rad))
-                elif kind == "box":
-                    if len(rp["box"]) != 4:
-                        raise ValueError(f"{where}: a box is (y0, x0, y1, x1)")
-                    y0, x0, y1, x1 = [coord(v, "box coordinate", where) for v in rp["box"]]
-                    if not (0 <= y0 < y1 <= h and 0 <= x0 < x1 <= w):
-                        raise ValueError(f"{where}: box {(y0, x0, y1, x1)} is not 0 <= y0 < y1 <= {h}, 0 <= x0 < x1 <= {w}")
-                    prims.append((g, 1, y0, x0, y1, x1))
-                    radii.append(-1)
-                else:
-                    m = rle_to_mask(rp["rle"]) if kind == "rle" else rp["mask"]
-                    if not torch.is_tensor(m):
-                        m = np.asarray(m)
-                    if tuple(m.shape) != (h, w):
-                        raise ValueError(f"{where}: a mask of shape {tuple(m.shape)} for an image of {(h, w)}")
-                    if m.dtype not in (torch.uint8, torch.bool, np.dtype(np.uint8), np.dtype(np.bool_)):
-                        raise ValueError(f"{where}: a mask of dtype {m.dtype} (uint8 or bool)")
-                    if torch.is_tensor(m) and m.device.type == "cpu":
-                        m = m.numpy()
-                    masks.append((g, m if torch.is_tensor(m) else np.ascontiguousarray(m != 0).view(np.uint8)))
-                    radii.append(-1)
-        R = len(radii)
-        if R == 0:
-            raise ValueError("regions given, but no prompt holds a <region> token")
-        arrays = {f"region_img{tag}": np.zeros(R, np.int32),                                   # every region pools from the session's image
-                  f"region_prims{tag}": np.asarray(prims, np.int32).reshape(-1, 6), f"region_radii{tag}": np.asarray(radii, np.int32)}
-        for g, m in masks:
-            if not torch.is_tensor(m):
-                arrays[f"region_mask{tag}_{g}"] = m.reshape(-1)
-        return {"tag": tag, "R": R, "counts": counts, "hw": (h, w), "tables": (h, w, nh, nw, ph, pw), "masks": masks, "arrays": arrays,
-                "max_radius": max([0] + radii)}
-
-    def _region_prompt_masks(self, session, rp, dv, total, tables=None):
-        """Device side, in front of the read-back: one launch each of rasterize, dilate and resize + pad for the R regions of `rp`; `total` (R) int32
-        zeroed, receives the pixel totals of the resized masks.  Returns (masks (R, S, S) uint8, row_cnt (R, S)).  Without a session: `tables`,
-        the (row, column) index tables of `rp["tables"]` on the device."""
-        o = self.ops
-        tag, R, (h, w) = rp["tag"], rp["R"], rp["hw"]
-        tabs = (rp["tables"],) + tuple(tables) if session is None else session.region_tables
-        if tabs is None or tabs[0] != rp["tables"]:
-            from .preprocess import nearest_pad_tables
-            rows, cols = nearest_pad_tables(*rp["tables"])
-            tabs = session.region_tables = (rp["tables"], self._dev_i32(rows), self._dev_i32(cols))
-        raw = o.mask_rasterize(dv[f"region_prims{tag}"].view(-1, 6), R, h, w)
-        for g, m in rp["masks"]:                                  # mask prompts: into their (zeroed) plane as they are
-            if torch.is_tensor(m):
-                m = m.to(self.device).contiguous()
-                src = m.view(torch.uint8) if m.dtype == torch.bool else m
-            else:
-                src = dv[f"region_mask{tag}_{g}"]
-            o.copy_(raw[g], src.view(h, w))
-        dil = o.mask_dilate_disc(raw, dv[f"region_radii{tag}"], rp["max_radius"])
-        return o.mask_resize_nearest_pad(dil, tabs[1], tabs[2], total=total)
-
-    def _region_prompt_ranks(self, rp, totals, sampler):
-        """Behind the read-back: `sampler(m, n)` per region in order (prompt by prompt, region by region) -> (R, n) int32 ranks into each region's
-        non-zero pixels.  A region without a pixel is an error here (the reference would fail in randint(0, 0))."""
-        n = self.cfg.region_points
-        out, g = [], 0
-        for b, k in enumerate(rp["counts"]):
-            for j in range(k):
-                m = int(totals[g])
-                if m <= 0:
-                    raise ValueError(f"prompt {b}, region {j}: no pixel of the prompt is left after the resize to the model's input size")
-                idx = torch.as_tensor(sampler(m, n)).reshape(-1).to(torch.int32)
-                if idx.numel() != n:
-                    raise ValueError(f"prompt {b}, region {j}: the region_index_sampler returned {idx.numel()} ranks, {n} are needed")
-                out.append(idx)
-                g += 1
-        return torch.stack(out) if out else torch.zeros(0, n, dtype=torch.int32)
-
-    def _region_pick(self, res):
-        """`pick=True`: per region the best query (first arg-max of `instances.scores`' column), its score and its binary mask as bytes, from a
-        post-processed region result that `_finalize` has not sliced yet."""
-        o = self.ops
-        _, scores, inst_masks, _ = res["_pending"]
-        q, s = o.region_best(scores if scores.is_contiguous() else scores.contiguous())
-        out = {"picked_query": o.to_i64(q), "picked_scores": s, "picked_masks": o.mask_gather_u8(inst_masks, q)}
-        if self.mask_boxes:                      # the picked queries' planes through the index list: no gather copy
-            out["picked_boxes"], out["picked_areas"] = o.mask_boxes(inst_masks, index=q)
-        return out
-
-    @torch.no_grad()
-    def segment(self, session: "ImageSession", input_ids, attention_mask=None, *, seg_info=None, class_name_ids=None,
-                class_name_embedding_indices=None, cls_indices=None, token_refer_id=None, refer_embedding_indices=None, is_thing_list=None,
-                labels=None, region_point_sampler: Callable = default_region_point_sampler, postprocess: bool = True,
-                stages: Optional[dict] = None, regions=None, region_index_sampler: Callable = default_region_index_sampler, pick: bool = True):
-        """N >= 1 prompts of the model's task on the session's image: what `eval_seg` returns for a batch of N copies of that image with these
-        prompts (a list of N result dicts), without running the vision side again and with a Phi pass over the rows behind the shared prefix
-        only.  Prompt-side keywords as eval_seg; `seg_info`: per prompt (region masks / ground truth under "instances", geometry), default the
-        session's entry for every prompt.  All prompts must agree on the tokens up to and including their one <image> (ValueError otherwise).
-        postprocess=False: the predictor outputs per prompt, as `forward_logits`; `stages`: filled as by `forward_logits(stages=...)` with the
-        suffix rows' `inputs_embeds` / `hidden_states`.
-
-        `regions` (region task): the region prompts as GEOMETRY instead of `instances.region_masks` -- per prompt a list with one dict per <region>
-        token, in pixels of the ORIGINAL image (the (h, w) of the session's `seg_info["transforms"]["resize"]`):
-            {"points": [(y, x), ...]}      discs of radius 10 ("radius": k overrides it, 0..16)
-            {"scribble": [(y, x), ...]}    the stroke's pixels, radius 5 (same override)
-            {"box": (y0, x0, y1, x1)}      half-open, 0 <= y0 < y1 <= h, 0 <= x0 < x1 <= w; not dilated
-            {"mask": (h, w) uint8 / bool array or tensor, host or device}   used as it is (non-zero = set)
-            {"rle": COCO RLE dict}         decoded on the host (preprocess.rle_to_mask), then a mask
-        The prompt is drawn, dilated, resized + padded and sampled on the device (psalm_mask_rasterize, psalm_mask_dilate_disc,
-        psalm_mask_resize_nearest_pad, psalm_mask_select_points: one launch each per call, one read-back of the R pixel totals);
-        `region_index_sampler(m, n)` draws n ranks into the m pixels of a region, prompt by prompt, region by region.  The results equal, bit for
-        bit, those of the host path on `apply_segmentation(enhance_with_circles(mask, radius), transforms)` as `region_masks` under
-        `region_point_sampler = lambda nz, k: region_index_sampler(nz.shape[0], k)`.  With `regions`, `gt` is returned only where the prompt's
-        seg_info carries `instances.gt_masks`, and `pick=True` adds `picked_query` (R) int64, `picked_scores` (R) float32, `picked_masks`
-        (R, H, W) uint8 (device tensors): per region the first arg-max of `instances.scores` and that query's mask -- and, with the model's
-        `mask_boxes` switch on, `picked_boxes` (R, 4) float32 / `picked_areas` (R) int32 of those masks."""
-        self._session_mode_check()
-        if not isinstance(session, ImageSession) or session.model is not self:
-            raise ValueError("segment: this session was made by another model (or replica)")
-        if session.version != self._weights_version:
-            raise ValueError("segment: the model's weights were prepared again after this session was made; encode the image again")
-        if self.seg_task == "panoptic" and postprocess:
-            assert is_thing_list is not None, "is_thing_list need to be given"
-            self.is_thing_list = is_thing_list
-        o, w, cfg = self.ops, self.w, self.cfg
-        if input_ids.dim() == 1:
-            input_ids = input_ids[None]
-        N = int(input_ids.shape[0])
-        if seg_info is None:
-            seg_info = [session.seg_info if session.seg_info is not None else {}] * N
-        if len(seg_info) != N:
-            raise ValueError("segment: one seg_info entry per prompt")
-        n_img = session.n_img
-        arrays = {}
-        n_regions = None
-        rp = None
-        if regions is not None:
-            try:
-                rp = self._region_prompt_plan(session, input_ids, seg_info, regions)
-            except ValueError as e:
-                raise ValueError(f"segment: {e}") from None
-            n_regions = rp["counts"]
-            arrays.update(rp["arrays"])
-        elif bool((input_ids == REGION_TOKEN_INDEX).any()):
-            pts, n_regions = self.region_points([s_["instances"].region_masks.tensor for s_ in seg_info], region_point_sampler)
-            arrays["region_img"] = np.zeros(sum(n_regions), np.int32)                 # every region pools from the session's image
-            arrays["region_pts"] = np.ascontiguousarray(pts.numpy(), np.float32)
-        sp = self._session_plan(session, input_ids, attention_mask, class_name_ids, cls_indices, token_refer_id, n_regions,
-                                class_name_embedding_indices is not None, refer_embedding_indices is not None)
-        P, S = sp["P"], sp["S"]
-        arrays["sid"], arrays["srow"], arrays["kmask"] = sp["sid"].reshape(-1), sp["srow"].reshape(-1), sp["kmask"].reshape(-1)
-        for name in ("seg", "cls", "refer", "region"):
-            if sp[name] is not None:
-                arrays[name + "_off"], arrays[name + "_rows"] = sp[name]
-        blob, layout = self._pack(arrays)
-        dv = self._views(torch.from_numpy(blob).to(self.device), layout)
-        if rp is not None and rp["R"]:
-            total = o.zeros(rp["R"], dtype=torch.int32)
-            rmasks, row_cnt = self._region_prompt_masks(session, rp, dv, total)
-        cache = self._session_prefix(session, sp)
-        region_feats = None
-        if rp is not None and rp["R"]:
-            try:
-                idx = self._region_prompt_ranks(rp, total.cpu().tolist(), region_index_sampler)       # the call's ONE read-back before the results
-            except ValueError as e:
-                raise ValueError(f"segment: {e}") from None
-            side = int(math.sqrt(n_img))
-            region_feats = o.region_pool(session.image_tokens, dv["region_img"], o.mask_select_points(rmasks, row_cnt, idx.to(self.device)), side,
-                                         side, n_img)
-        elif n_regions is not None and rp is None:
-            side = int(math.sqrt(n_img))
-            region_feats = o.region_pool(session.image_tokens, dv["region_img"], dv["region_pts"].view(sum(n_regions), -1, 2), side, side, n_img)
-        embeds = o.gather_rows([w["embed"], session.image_tokens, w["seg_query"], region_feats], dv["sid"], dv["srow"], cfg.hidden_size,
-                               out_dtype=torch.float32)
-        hidden = self._llm_session(embeds, dv["kmask"].view(N, S), N, S, P, cache, suffix=True)
-        if stages is not None:
-            Sr = sp["S_real"]
-            stages.update(feats=session.feats, image_tokens=session.image_tokens, prefix_len=P, lengths=sp["lens"],
-                          inputs_embeds=embeds.view(N, S, -1)[:, :Sr], hidden_states=hidden.view(N, S, -1)[:, :Sr])
-        Q = cfg.md_queries
-        seg_q = o.gemm(o.segment_mean(hidden, dv["seg_off"], dv["seg_rows"], out_dtype=self.adt), w["seg_query_projector.w"],
-                       w["seg_query_projector.b"], out_dtype=torch.float32)
-        cls_emb = seg_emb = reg_emb = None
-        if "cls_off" in dv:
-            cls_emb = o.gemm(o.segment_mean(hidden, dv["cls_off"], dv["cls_rows"], out_dtype=self.adt), w["class_name_projector.w"],
-                             w["class_name_projector.b"], out_dtype=self.wdt)
-        if "refer_off" in dv:
-            seg_emb = o.gemm(o.segment_mean(hidden, dv["refer_off"], dv["refer_rows"], out_dtype=self.adt), w["SEG_token_projector.w"],
-                             w["SEG_token_projector.b"], out_dtype=self.wdt)
-        if "region_off" in dv:
-            reg_emb = o.gemm(o.segment_mean(hidden, dv["region_off"], dv["region_rows"], out_dtype=self.adt), w["region_projector.w"],
-                             w["region_projector.b"], out_dtype=self.adt)
-        if stages is not None:
-            stages.update(seg_query=seg_q.view(N, Q, -1), class_name_embedding=cls_emb, SEG_embedding=seg_emb, region_embedding=reg_emb,
-                          mask_features=[session.mask_features] * N, multi_scale_features=[session.multi_scale_features] * N)
-        mf, ms, shapes, mfs = session.mask_features, session.multi_scale_features, session.shapes, session.mask_features_size
-        Hi, Wi = int(session.images.shape[2]), int(session.images.shape[3])
-        outs = []
-        c0 = r0 = 0
-        prompts = []
-        for b in range(N):
-            nc = sp["n_cls"][b]
-            ce = cls_emb[c0:c0 + nc] if cls_emb is not None else None
-            c0 += nc
-            se = seg_emb[b:b + 1] if seg_emb is not None else None
-            re = None
-            if reg_emb is not None:
-                re = reg_emb[r0:r0 + n_regions[b]]
-                r0 += n_regions[b]
-            prompts.append((seg_q[b * Q:(b + 1) * Q], se, ce, re))
-        decoded = self._decode_batched(session, prompts)         # (None: the per-prompt loop below)
-        for b in range(N):
-            sq, se, ce, re = prompts[b]
-            r = decoded[b] if decoded is not None else self.predictor(ms, shapes, mf, mfs, sq, se, ce, re,
-                                                                      kv=self._session_kv(session, n_regions[b] if n_regions else 0))
-            if not postprocess:
-                outs.append(r)
-                continue
-            res = self._postprocess(r, self._post_sizes(Hi, Wi, seg_info[b], cfg.size_divisibility))
-            picked = self._region_pick(res) if rp is not None and pick and n_regions[b] else {}
-            outs.append(self._finalize(res, seg_info[b], gt_optional=rp is not None))
-            outs[-1].update(picked)
-        return outs
-
-    @torch.no_grad()
-    def segment_many(self, requests, *, postprocess: bool = True, region_point_sampler: Callable = default_region_point_sampler,
-                     stages: Optional[dict] = None, region_index_sampler: Callable = default_region_index_sampler, pick: bool = True):
-        """Prompts on SEVERAL images in one Phi pass: `requests` is a list of (session, kwargs) pairs, kwargs what `segment(session, **kwargs)` takes
-        for the prompt side (input_ids, attention_mask, seg_info, class_name_ids, ..., is_thing_list).  Returns one list per request, each what
-        `segment(session, **kwargs)` returns.  Every request obeys segment's rules on its own (session of this model and weights version, its
-        prompts agree up to and including <image>); requests may differ in image size, n_img, leading text and so in prefix length.  A session may
-        appear in several requests -- they share its one prefix cache, so they must share their leading text too.
-        The prefix caches are built or reused per session as `segment` does it; then ONE suffix pass runs over the prompts of all requests (S = the
-        bucketed maximum of their suffix lengths) with the grouped prefix attention, the row-set means and projector GEMMs run once, and the
-        predictor and post-processing run per prompt from its own session.
-        Region task: `region_point_sampler` is called request by request in list order, inside a request prompt by prompt and region by region --
-        the order a loop of `segment` calls over `requests` draws in.
-        A request's kwargs may carry `regions` (and `pick`) as `segment` takes them: the prompt masks are made per request on the device, ONE read-back
-        brings the pixel totals of all requests, and `region_index_sampler` is called request by request, prompt by prompt, region by region.  Either
-        every region request of a call gives `regions` or none does (the two paths draw from the sampler at different points of the call).
-        `stages`: filled with the suffix rows' `inputs_embeds` / `hidden_states` ((N, S, hidden), N = all prompts in request order), `prefix_lens`
-        (per prompt) and `lengths`."""
-        self._session_mode_check()
-        requests = list(requests)
-        if not requests:
-            raise ValueError("segment_many: an empty request list")
-        o, w, cfg = self.ops, self.w, self.cfg
-        plans, arrays = [], {}
-        any_regions = False
-        rps = []                                                  # per request: the plan of its `regions`, or None
-        for r, (session, kw) in enumerate(requests):
-            if not isinstance(session, ImageSession) or session.model is not self:
-                raise ValueError(f"segment_many: request {r}: this session was made by another model (or replica)")
-            if session.version != self._weights_version:
-                raise ValueError(f"segment_many: request {r}: the model's weights were prepared again after this session was made; encode the image again")
-            kw = dict(kw)
-            if self.seg_task == "panoptic" and postprocess:
-                assert kw.get("is_thing_list") is not None, "is_thing_list need to be given"
-                self.is_thing_list = kw["is_thing_list"]
-            ids = kw["input_ids"]
-            if ids.dim() == 1:
-                ids = ids[None]
-            N = int(ids.shape[0])
-            seg_info = kw.get("seg_info")
-            if seg_info is None:
-                seg_info = [session.seg_info if session.seg_info is not None else {}] * N
-            if len(seg_info) != N:
-                raise ValueError(f"segment_many: request {r}: one seg_info entry per prompt")
-            n_regions = None
-            rps.append(None)
-            if kw.get("regions") is not None:
-                try:
-                    rps[r] = self._region_prompt_plan(session, ids, seg_info, kw["regions"], tag=str(r))
-                except ValueError as e:
-                    raise ValueError(f"segment_many: request {r}: {e}") from None
-                n_regions = rps[r]["counts"]
-                arrays.update(rps[r]["arrays"])
-                any_regions = True
-            elif bool((ids == REGION_TOKEN_INDEX).any()):
-                pts, n_regions = self.region_points([s_["instances"].region_masks.tensor for s_ in seg_info], region_point_sampler)
-                arrays[f"region_img{r}"] = np.zeros(sum(n_regions), np.int32)         # every region pools from its own session's image
-                arrays[f"region_pts{r}"] = np.ascontiguousarray(pts.numpy(), np.float32)
-                any_regions = True
-            try:
-                sp = self._session_plan(session, ids, kw.get("attention_mask"), kw.get("class_name_ids"), kw.get("cls_indices"),
-                                        kw.get("token_refer_id"), n_regions, kw.get("class_name_embedding_indices") is not None,
-                                        kw.get("refer_embedding_indices") is not None)
-            except ValueError as e:
-                raise ValueError(f"segment_many: request {r}: {e}") from None
-            plans.append((session, sp, N, seg_info, n_regions))
-        if any(p is not None for p in rps) and any(p is None and pl[4] is not None for p, pl in zip(rps, plans)):
-            raise ValueError("segment_many: some requests give `regions`, others instances.region_masks: one kind per call")
-        for name in ("cls", "refer", "region"):
-            if len({sp[name] is None for _, sp, _, _, _ in plans}) != 1:
-                raise ValueError(f"segment_many: some requests carry {name} rows and some do not; all requests are prompts of the model's one task")
-        # the prefix caches, per session as segment builds / reuses them (a session listed twice: once)
-        caches, cache_of, seen = [], [], {}
-        for r, (session, sp, N, _, _) in enumerate(plans):
-            if id(session) in seen:
-                c, first = seen[id(session)]
-                if plans[first][1]["key"] != sp["key"] or plans[first][1]["P"] != sp["P"]:
-                    raise ValueError(f"segment_many: requests {first} and {r} share a session but not their leading text (one prefix cache per session)")
-            else:
-                c = len(caches)
-                caches.append(self._session_prefix(session, sp))
-                seen[id(session)] = (c, r)
-            cache_of += [c] * N
-        Nt = len(cache_of)
-        S = max(sp["S"] for _, sp, _, _, _ in plans)
-        P_max = max(sp["P"] for _, sp, _, _, _ in plans)
-        rhost = o.prefix_ref_table(caches, cache_of)
-        # the suffix plans side by side: prompt g of the call = prompt b of its request; rows re-based from (b, s) of (N_r, S_r) to (g, s) of (Nt, S)
-        sid = np.full((Nt, S), -1, np.int32)
-        srow = np.zeros((Nt, S), np.int32)
-        kmask = np.zeros((Nt, S), np.uint8)
-        sets = {name: ([np.zeros(1, np.int32)], []) for name in ("seg", "cls", "refer", "region") if plans[0][1][name] is not None}
-        g0 = reg0 = 0
-        for session, sp, N, _, n_regions in plans:
-            Sr = sp["S"]
-            sid[g0:g0 + N, :Sr], kmask[g0:g0 + N, :Sr] = sp["sid"], sp["kmask"]
-            assert not (sp["sid"] == 1).any(), "image rows live in the prefix"
-            srow[g0:g0 + N, :Sr] = sp["srow"] + np.where(sp["sid"] == 3, reg0, 0).astype(np.int32)      # region rows: into the concatenated features
-            for name, (offs, rows) in sets.items():
-                off, rw = sp[name]
-                n = int(off[-1])
-                rw = rw[:n].astype(np.int64)                     # (behind off[-1]: _session_plan's bucket padding)
-                rows.append(((rw // Sr + g0) * S + rw % Sr).astype(np.int32))
-                offs.append((off[1:].astype(np.int64) + int(offs[-1][-1])).astype(np.int32))
-            g0 += N
-            reg0 += sum(n_regions) if n_regions else 0
-        q = max(int(self.len_bucket or 0), 1)
-        for name, (offs, rows) in sets.items():
-            rows = np.concatenate(rows) if rows else np.zeros(0, np.int32)
-            if name != "seg" and q > 1:                           # (as _session_plan buckets the row-set lengths)
-                n = (rows.shape[0] + q - 1) // q * q
-                rows = np.concatenate((rows, np.zeros(max(n, q) - rows.shape[0], np.int32)))
-            arrays[name + "_off"], arrays[name + "_rows"] = np.concatenate(offs), rows
-        arrays["sid"], arrays["srow"], arrays["kmask"] = sid.reshape(-1), srow.reshape(-1), kmask.reshape(-1)
-        arrays["refs"] = rhost.view(np.uint8).reshape(-1)
-        blob, layout = self._pack(arrays)
-        dv = self._views(torch.from_numpy(blob).to(self.device), layout)
-        region_feats = None
-        dev_pts = {}
-        if any(p is not None for p in rps):                      # `regions`: masks per request, ONE read-back of all totals, then the sampler in request order
-            total = o.zeros(sum(p["R"] for p in rps if p is not None), dtype=torch.int32)
-            made, g0 = {}, 0
-            for r, p in enumerate(rps):
-                if p is not None:
-                    made[r] = self._region_prompt_masks(plans[r][0], p, dv, total[g0:g0 + p["R"]])
-                    g0 += p["R"]
-            totals = total.cpu().tolist()
-            ranks, g0 = {}, 0
-            for r, p in enumerate(rps):
-                if p is not None:
-                    try:
-                        ranks[r] = self._region_prompt_ranks(p, totals[g0:g0 + p["R"]], region_index_sampler)
-                    except ValueError as e:
-                        raise ValueError(f"segment_many: request {r}: {e}") from None
-                    g0 += p["R"]
-            idx = torch.cat([ranks[r] for r in sorted(ranks)]).to(self.device)
-            g0 = 0
-            for r in sorted(ranks):
-                dev_pts[r] = o.mask_select_points(made[r][0], made[r][1], idx[g0:g0 + rps[r]["R"]])
-                g0 += rps[r]["R"]
-        if any_regions:
-            feats = []
-            for r, (session, sp, N, _, n_regions) in enumerate(plans):
-                if n_regions is None:
-                    continue
-                side = int(math.sqrt(session.n_img))
-                pts = dev_pts[r] if r in dev_pts else dv[f"region_pts{r}"].view(sum(n_regions), -1, 2)
-                feats.append(o.region_pool(session.image_tokens, dv[f"region_img{r}"], pts, side, side, session.n_img))
-            region_feats = feats[0] if len(feats) == 1 else torch.cat(feats)
-        embeds = o.gather_rows([w["embed"], None, w["seg_query"], region_feats], dv["sid"], dv["srow"], cfg.hidden_size, out_dtype=torch.float32)
-        hidden = self._llm_session(embeds, dv["kmask"].view(Nt, S), Nt, S, P_max, None, suffix=True, refs=(dv["refs"], rhost))
-        if stages is not None:
-            stages.update(prefix_lens=[sp["P"] for _, sp, N, _, _ in plans for _ in range(N)],
-                          lengths=[l_ for _, sp, _, _, _ in plans for l_ in sp["lens"]],
-                          inputs_embeds=embeds.view(Nt, S, -1), hidden_states=hidden.view(Nt, S, -1))
-        Q = cfg.md_queries
-        seg_q = o.gemm(o.segment_mean(hidden, dv["seg_off"], dv["seg_rows"], out_dtype=self.adt), w["seg_query_projector.w"],
-                       w["seg_query_projector.b"], out_dtype=torch.float32)
-        cls_emb = seg_emb = reg_emb = None
-        if "cls_off" in dv:
-            cls_emb = o.gemm(o.segment_mean(hidden, dv["cls_off"], dv["cls_rows"], out_dtype=self.adt), w["class_name_projector.w"],
-                             w["class_name_projector.b"], out_dtype=self.wdt)
-        if "refer_off" in dv:
-            seg_emb = o.gemm(o.segment_mean(hidden, dv["refer_off"], dv["refer_rows"], out_dtype=self.adt), w["SEG_token_projector.w"],
-                             w["SEG_token_projector.b"], out_dtype=self.wdt)
-        if "region_off" in dv:
-            reg_emb = o.gemm(o.segment_mean(hidden, dv["region_off"], dv["region_rows"], out_dtype=self.adt), w["region_projector.w"],
-                             w["region_projector.b"], out_dtype=self.adt)
-        results = []
-        g = c0 = r0 = 0
-        # every prompt's decoder operands, then the prompts of all requests naming one session as one batch of the decoder (different sessions have
-        # different K / V: separate calls)
-        prompts, by_session = [], {}
-        for session, sp, N, seg_info, n_regions in plans:
-            for b in range(N):
-                nc = sp["n_cls"][b]
-                ce = cls_emb[c0:c0 + nc] if cls_emb is not None else None
-                c0 += nc
-                se = seg_emb[g:g + 1] if seg_emb is not None else None
-                re = None
-                if reg_emb is not None:
-                    re = reg_emb[r0:r0 + n_regions[b]]
-                    r0 += n_regions[b]
-                prompts.append((seg_q[g * Q:(g + 1) * Q], se, ce, re))
-                by_session.setdefault(id(session), (session, []))[1].append(g)
-                g += 1
-        decoded = {}
-        for session, gs in by_session.values():
-            rs = self._decode_batched(session, [prompts[i] for i in gs])
-            if rs is not None:
-                decoded.update(zip(gs, rs))
-        g = 0
-        for ri, (session, sp, N, seg_info, n_regions) in enumerate(plans):
-            mf, ms, shapes, mfs = session.mask_features, session.multi_scale_features, session.shapes, session.mask_features_size
-            Hi, Wi = int(session.images.shape[2]), int(session.images.shape[3])
-            outs = []
-            for b in range(N):
-                sq, se, ce, re = prompts[g]
-                res = decoded[g] if g in decoded else self.predictor(ms, shapes, mf, mfs, sq, se, ce, re,
-                                                                     kv=self._session_kv(session, n_regions[b] if n_regions else 0))
-                g += 1
-                if postprocess:
-                    res = self._postprocess(res, self._post_sizes(Hi, Wi, seg_info[b], cfg.size_divisibility))
-                    picked = self._region_pick(res) if rps[ri] is not None and requests[ri][1].get("pick", pick) and n_regions[b] else {}
-                    res = self._finalize(res, seg_info[b], gt_optional=rps[ri] is not None)
-                    res.update(picked)
-                outs.append(res)
-            results.append(outs)
-        return results
 
     # ======================================================================================= post-processing + eval_seg
     def _semantic(self, mflat, probsT, Kpad, want_mask_score=False):

@@ -36,7 +36,8 @@ from typing import Callable, List, Optional
 import numpy as np
 import torch
 
-from .model import PSALM, ImageSession, default_region_index_sampler  # noqa: F401  (the sampler lives next to its point-sampler twin; re-exported here)
+from .model import PSALM
+from .session import ImageSession, default_region_index_sampler  # noqa: F401  (the sampler lives next to its point-sampler twin; re-exported here)
 from .config import REGION_TOKEN_INDEX
 from .preprocess import nearest_pad_tables
 
