@@ -39,8 +39,10 @@ const char* psalm_last_error(void);
  * 11: the mask decoder over all prompts of an image session: psalm_mha_attention_f32_shared (+ _workspace), psalm_gemm_f32_rows[_pair],
  *    psalm_gemm_f32_grouped, psalm_predictor_kv_bytes, the stage-level psalm_predictor_forward_batched (+ _workspace).
  * 12: region prompts of image sessions: psalm_mask_rasterize, psalm_mask_dilate_disc, psalm_region_best, psalm_mask_gather_u8.
- * 13: boxes and areas from masks: psalm_mask_boxes (+ _workspace), psalm_label_boxes. */
-#define PSALM_ABI_VERSION 13
+ * 13: boxes and areas from masks: psalm_mask_boxes (+ _workspace), psalm_label_boxes.
+ * 14: all-pairs mask overlap on bit planes: psalm_mask_bits_words, psalm_mask_pack_bits, psalm_mask_unpack_bits, psalm_mask_pair_counts,
+ *    psalm_mask_nms, psalm_mask_paint_bits. */
+#define PSALM_ABI_VERSION 14
 int psalm_abi_version(void);
 const char* psalm_backend(void); /* "hip-gfx950" */
 
@@ -787,6 +789,44 @@ int psalm_mask_boxes(const void* masks, int dtype_is_u8, int n, int H, int W, co
  * is v, the same box convention; all zeros for a value that does not occur; label values outside [0, n_ids) are ignored.  1 <= n_ids <= 256,
  * H * W < 2^31.  `table` is zeroed by the call itself (a memset node on `stream`) and serves as the accumulator: no workspace. */
 int psalm_label_boxes(const void* labels, int dtype_is_u8, int H, int W, int n_ids, int* table, void* stream);
+
+/* ------------------------------------------------------------------------------------------------------------------
+ * All-pairs mask overlap on bit planes (csrc/maskpairs.hip; PSALM.segment_everything, psalm_amd/evalout.py mask_pair_counts / mask_nms): pack
+ * the masks once, count popcount(a_i & b_j) for all pairs, run greedy NMS on the counts, paint a label map from the same bits.
+ * Bit-plane layout, plane-flat: word w, bit b of a plane is pixel 64 w + b in row-major order; nw = ceil(HW / 64) words per plane; the unused
+ * high bits of the last word are ZERO (every consumer relies on it).  Bit buffers are 8-byte aligned.  All results are integers, partial sums
+ * are combined with integer atomics: exact and independent of the order of arrival.  Nothing allocates or synchronises; what a call accumulates
+ * into it zeroes itself (a memset node on `stream`). */
+/* nw for planes of HW pixels; -1 for HW <= 0 or HW >= 2^31. */
+long psalm_mask_bits_words(long HW);
+/* masks (n,HW) contiguous, float32 (dtype_is_u8 = 0; set when f > 0: NaN, -0.0 and negatives are not) or bytes (1; set when != 0) -- the tests of
+ * psalm_binarize_gather and psalm_mask_boxes.  Output row i is plane index_dev[i] (m entries, int32 on the device; an entry outside [0, n) gives
+ * an empty plane), or plane i when index_dev is NULL (then m must equal n).  bits (m,nw); areas (m) i32 = set pixels, may be NULL.  Planes and
+ * rows need no alignment beyond the element's own; m <= 65535; m == 0 is a no-op. */
+int psalm_mask_pack_bits(const void* masks, int dtype_is_u8, int n, long HW, const int* index_dev, int m, unsigned long long* bits, int* areas,
+                         void* stream);
+/* out (k,HW) bytes of 0 / 1 from bit rows rows_dev[i] (int32 on the device; every non-negative entry must name a row of `bits`), or from row i
+ * when rows_dev is NULL; a negative row index gives an all-zero plane.  nw == psalm_mask_bits_words(HW); k <= 65535; k == 0 is a no-op. */
+int psalm_mask_unpack_bits(const unsigned long long* bits, long nw, const int* rows_dev, int k, long HW, unsigned char* out, void* stream);
+/* inter (ma,mb) i32: inter[i][j] = popcount(a_i & b_j) summed over the nw words.  bits_b == bits_a is allowed; the full matrix is written either
+ * way.  1 <= ma, mb <= 1024, 1 <= nw <= 2^25.  The union is not computed here: it is area_i + area_j - inter.  A block owns a 64 x 64 tile of
+ * pairs and stages 32-word chunks of both operands in LDS; K is split over blocks (at least 64 words each) until about 1024 blocks are in
+ * flight. */
+int psalm_mask_pair_counts(const unsigned long long* bits_a, int ma, const unsigned long long* bits_b, int mb, long nw, int* inter, void* stream);
+/* Greedy NMS.  inter (m,m) i32, areas (m) i32, scores (m) f32 without NaN, 1 <= m <= 1024.
+ *   Rank order: descending score, equal scores the lowest index first (the tie rule of psalm_region_best and psalm_video_pick).
+ *   Filtering: a candidate with areas[i] < min_area or scores[i] < min_score is filtered: keep[i] = -1, owner[i] = -1.
+ *   Walk the rest in rank order: candidate i is suppressed by the FIRST already-kept candidate j with
+ *       thr_den * inter[i][j] > thr_num * (areas[i] + areas[j] - inter[i][j])         (64-bit products: exactly IoU > thr_num / thr_den,
+ *   false at equality and for a zero union): keep[i] = 0, owner[i] = j.  Otherwise i is kept: keep[i] = 1, owner[i] = i.  A suppressed
+ *   candidate suppresses nothing.
+ * kept (m + 1) i32: kept[0] = K, kept[1..K] the kept indices in rank order, the rest -1.  0 < thr_num <= thr_den <= 4096. */
+int psalm_mask_nms(const int* inter, const int* areas, const float* scores, int m, int thr_num, int thr_den, int min_area, float min_score, int* kept,
+                   int* keep, int* owner, void* stream);
+/* labels (HW) i32: labels[p] = 1 + the smallest k < K such that bit row kept[1 + k] has pixel p set, 0 if none does -- the best-scoring mask wins
+ * a contested pixel.  K = kept[0] is read on the device (no host synchronisation in front of this call); m <= 1024, the number of bit rows, bounds K and the
+ * entries (one outside [0, m) is passed over). */
+int psalm_mask_paint_bits(const unsigned long long* bits, long nw, const int* kept, int m, long HW, int* labels, void* stream);
 
 #ifdef __cplusplus
 }

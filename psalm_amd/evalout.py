@@ -14,6 +14,8 @@ with one tiny RCCL all-reduce (`psalm_amd.dist.reduce_metrics`, the role of Aver
     fuse_masks_by_score(pred_masks, scores, thr)  eval_grefcoco.py:113-131,277-285 (gRefCOCO: union of the candidates above thr, else top-1)
     IoUMeters                                     referring_segmentation.py:139-177 + :58-79 (cIoU / gIoU bookkeeping + all-reduce)
     mask_boxes(masks) / label_boxes(labels, n)    llava_phi.py:319,395,438-440 (the commented-out `BitMasks(..).get_bounding_boxes()`) -> boxes, areas
+    mask_pair_counts(masks_a, masks_b)            COCO mask matching / DAVIS J: the prediction x ground-truth overlap matrix on bit planes
+    mask_nms(masks, scores, iou_thr)              greedy mask NMS under an exact rational IoU threshold (PSALM.segment_everything's rule)
     coco_instance_records(instances, image_id)    detectron2 instances_to_coco_json (instance_evaluation.py) -> the COCO result records
 """
 from __future__ import annotations
@@ -201,6 +203,72 @@ def label_boxes(labels: torch.Tensor, n_ids: int, ops=None) -> torch.Tensor:
     if not torch.is_tensor(labels) or labels.dim() != 2:
         raise H.PsalmHipError("label_boxes: an (H,W) int32 / uint8 id map")
     return o.label_boxes(_on_device(o, labels, (torch.int32, torch.uint8), "label_boxes"), n_ids)
+
+
+def _bit_planes(o, masks, what):
+    if not torch.is_tensor(masks) or masks.dim() != 3:
+        raise H.PsalmHipError(f"{what}: (n,H,W) float32 / uint8 / bool masks")
+    masks = _on_device(o, masks, (torch.float32, torch.uint8, torch.bool), what)
+    if not 1 <= masks.shape[0] <= o.MASK_PAIRS_MAX:
+        raise H.PsalmHipError(f"{what}: {masks.shape[0]} masks (1..{o.MASK_PAIRS_MAX})")
+    return masks, o.mask_pack_bits(masks)
+
+
+def mask_pair_counts(masks_a: torch.Tensor, masks_b: Optional[torch.Tensor] = None, ops=None):
+    """All-pairs mask overlap on the device: masks_a (na,H,W), masks_b (nb,H,W) float32 (set: > 0) | uint8 | bool (set: != 0), masks_b=None: a
+    against itself; 1 <= na, nb <= 1024 -> (inter (na,nb) int32 = pixels set in both, areas_a (na) int32, areas_b (nb) int32).  The masks are
+    packed into bit planes once (psalm_mask_pack_bits) and every pair is a popcount over 64-pixel words (psalm_mask_pair_counts).
+    `iou = inter / (areas_a[:, None] + areas_b[None] - inter)` gives the prediction x ground-truth matrix of COCO mask matching and DAVIS J
+    without moving a mask."""
+    o = _ops(ops)
+    a, (bits_a, areas_a) = _bit_planes(o, masks_a, "mask_pair_counts")
+    if masks_b is None:
+        return o.mask_pair_counts(bits_a), areas_a, areas_a
+    b, (bits_b, areas_b) = _bit_planes(o, masks_b, "mask_pair_counts")
+    if tuple(a.shape[1:]) != tuple(b.shape[1:]):
+        raise H.PsalmHipError(f"mask_pair_counts: masks of {tuple(a.shape[1:])} against masks of {tuple(b.shape[1:])}")
+    return o.mask_pair_counts(bits_a, bits_b), areas_a, areas_b
+
+
+def iou_fraction(iou_thr) -> Tuple[int, int]:
+    """The NMS threshold as the rational the kernels compare with: a (num, den) pair as it is, a float through
+    `Fraction(iou_thr).limit_denominator(4096)` (0.7 -> 7/10); it must lie in (0, 1] with a denominator <= 4096 (ValueError otherwise)."""
+    from fractions import Fraction
+    if isinstance(iou_thr, (tuple, list)):
+        if len(iou_thr) != 2 or any(isinstance(v, bool) or not isinstance(v, (int, np.integer)) for v in iou_thr):
+            raise ValueError(f"iou_thr {iou_thr!r}: a float or a (num, den) pair of integers")
+        num, den = int(iou_thr[0]), int(iou_thr[1])
+    else:
+        v = float(iou_thr)
+        if not 0.0 < v <= 1.0:                                        # (NaN fails both comparisons)
+            raise ValueError(f"iou_thr {iou_thr!r} outside (0, 1]")
+        f = Fraction(v).limit_denominator(4096)
+        num, den = f.numerator, f.denominator
+    if not 0 < num <= den <= 4096:
+        raise ValueError(f"iou_thr {iou_thr!r} = {num}/{den}: outside (0, 1] or a denominator above 4096")
+    return num, den
+
+
+def mask_nms(masks: torch.Tensor, scores: torch.Tensor, iou_thr=0.7, min_area: int = 1, min_score: Optional[float] = None, ops=None) -> dict:
+    """Greedy mask NMS on the device: masks (n,H,W) float32 | uint8 | bool, scores (n) float32 without NaN, 1 <= n <= 1024.  Candidates are
+    walked by descending score (equal scores: the lower index first); one with fewer than `min_area` pixels or a score below `min_score` is
+    filtered; one whose IoU with an already kept candidate EXCEEDS the threshold is suppressed by the first such candidate.  The rule is the
+    rational `Fraction(iou_thr).limit_denominator(4096)` (0.7 is 7/10; or give `iou_thr=(num, den)`) and it is strict: an IoU equal to the
+    threshold does not suppress; the comparison is made in integers.
+    -> {"kept": (K) int64 indices by descending score, "keep": (n) int32 1 kept / 0 suppressed / -1 filtered, "owner": (n) int32 the kept
+    candidate that stands for each (-1: filtered), "areas": (n) int32, "inter": (n,n) int32}, on the device.  One read-back: the `kept` block."""
+    o = _ops(ops)
+    num, den = iou_fraction(iou_thr)
+    masks, (bits, areas) = _bit_planes(o, masks, "mask_nms")
+    n = masks.shape[0]
+    if not torch.is_tensor(scores) or scores.dim() != 1 or scores.shape[0] != n:
+        raise H.PsalmHipError(f"mask_nms: (n) float32 scores for {n} masks")
+    sc = _on_device(o, scores, (torch.float32,), "mask_nms")
+    inter = o.mask_pair_counts(bits)
+    kept, keep, owner = o.mask_nms(inter, areas, sc, num, den, min_area=min_area, min_score=min_score)
+    K = int(kept.cpu()[0])                                            # the one read-back
+    kept = o.to_i64(kept[1:1 + K]) if K else torch.empty(0, dtype=torch.int64, device=o.device)
+    return {"kept": kept, "keep": keep, "owner": owner, "areas": areas, "inter": inter}
 
 
 def coco_instance_records(instances, image_id, category_ids: Optional[Sequence[int]] = None, ops=None) -> List[dict]:

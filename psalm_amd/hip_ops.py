@@ -49,7 +49,7 @@ def _dt(t: torch.Tensor) -> int:
         raise PsalmHipError(f"unsupported dtype {t.dtype} (float32 / bfloat16 only)")
 
 
-ABI_VERSION = 13       # == PSALM_ABI_VERSION of include/psalm_hip.h (tests/test_0_abi.py compares the two and the built library's answer)
+ABI_VERSION = 14       # == PSALM_ABI_VERSION of include/psalm_hip.h (tests/test_0_abi.py compares the two and the built library's answer)
 
 
 class _ProfiledLib:
@@ -1872,6 +1872,126 @@ class Ops:
         rc = self.lib.psalm_label_boxes(self._p(labels), 1 if labels.dtype == torch.uint8 else 0, Hh, Ww, n_ids, self._p(table), self._stream())
         self._check(rc, "psalm_label_boxes")
         return table
+
+    # ------------------------------------------------------------------ all-pairs mask overlap on bit planes (csrc/maskpairs.hip)
+    MASK_PAIRS_MAX = 1024
+
+    def mask_bits_words(self, HW) -> int:
+        """words per bit plane of HW pixels, ceil(HW / 64): psalm_mask_bits_words"""
+        fn = self._cdll_raw.psalm_mask_bits_words                      # (a host function: no launch to record)
+        fn.restype = c_long
+        nw = fn(c_long(int(HW)))
+        if nw < 0:
+            raise PsalmHipError(f"mask bit planes: {HW} pixels per plane (1 .. 2^31 - 1)")
+        return int(nw)
+
+    def _want_bits(self, bits, what):
+        if not torch.is_tensor(bits) or bits.dim() != 2 or bits.dtype != torch.int64 or not bits.is_contiguous():
+            raise PsalmHipError(f"{what}: bit planes (m,nw) as a contiguous int64 tensor, got {getattr(bits, 'dtype', type(bits))} "
+                                f"{tuple(getattr(bits, 'shape', ()))}")
+        return bits
+
+    def mask_pack_bits(self, masks, index=None, out_bits=None, out_areas=None, want_areas=True):
+        """masks (n,H,W) | (n,HW) float32 (set: > 0) | uint8 / bool (set: != 0) -> (bits (m,nw) int64: word w, bit b = pixel 64 w + b, the last word's
+        tail zero; areas (m) i32 = set pixels, None with want_areas=False): psalm_mask_pack_bits.  index (m) i32 on the device: the planes to pack
+        (an entry outside [0, n) gives an empty plane), default all n in order.  The outputs may be given (views of a caller-owned block)."""
+        if not torch.is_tensor(masks) or masks.dim() not in (2, 3) or masks.dtype not in (torch.float32, torch.uint8, torch.bool):
+            raise PsalmHipError(f"mask_pack_bits: masks (n,H,W) float32 / uint8 / bool, got {getattr(masks, 'dtype', type(masks))} "
+                                f"{tuple(getattr(masks, 'shape', ()))}")
+        if masks.dtype == torch.bool:
+            masks = masks.view(torch.uint8)
+        n = int(masks.shape[0])
+        HW = int(masks[0].numel()) if n else int(np.prod(masks.shape[1:]))
+        nw = self.mask_bits_words(HW)
+        m = n if index is None else int(index.numel())
+        if index is not None:
+            self._want(index, torch.int32, (m,), "mask_pack_bits index")
+        if m > 65535:
+            raise PsalmHipError(f"mask_pack_bits: {m} output rows (at most 65535)")
+        bits = self.empty(m, nw, dtype=torch.int64) if out_bits is None else self._want(out_bits, torch.int64, (m, nw), "mask_pack_bits out_bits")
+        areas = None
+        if want_areas or out_areas is not None:
+            areas = self.empty(m, dtype=torch.int32) if out_areas is None else self._want(out_areas, torch.int32, (m,), "mask_pack_bits out_areas")
+        rc = self.lib.psalm_mask_pack_bits(self._p(masks), 1 if masks.dtype == torch.uint8 else 0, n, c_long(HW), self._p(index), m, self._p(bits),
+                                           self._p(areas), self._stream())
+        self._check(rc, "psalm_mask_pack_bits")
+        return bits, areas
+
+    def mask_unpack_bits(self, bits, shape, rows=None, out=None):
+        """bits (m,nw) int64, shape = (H, W) (or the pixel count HW) -> (k,H,W) | (k,HW) uint8 of 0 / 1 from the bit rows rows[i] ((k) i32 on the
+        device, each below m; a negative entry gives an all-zero plane), default all m rows in order: psalm_mask_unpack_bits."""
+        self._want_bits(bits, "mask_unpack_bits")
+        dims = tuple(int(v) for v in shape) if isinstance(shape, (tuple, list)) else (int(shape),)
+        HW = int(np.prod(dims))
+        m, nw = bits.shape
+        if self.mask_bits_words(HW) != nw:
+            raise PsalmHipError(f"mask_unpack_bits: planes of {HW} pixels have {self.mask_bits_words(HW)} words, the bit rows have {nw}")
+        k = m if rows is None else int(rows.numel())
+        if rows is not None:
+            self._want(rows, torch.int32, (k,), "mask_unpack_bits rows")
+        if k > 65535:
+            raise PsalmHipError(f"mask_unpack_bits: {k} output rows (at most 65535)")
+        out = self.empty(k, *dims, dtype=torch.uint8) if out is None else self._want(out, torch.uint8, (k,) + dims, "mask_unpack_bits out")
+        rc = self.lib.psalm_mask_unpack_bits(self._p(bits), c_long(nw), self._p(rows), k, c_long(HW), self._p(out), self._stream())
+        self._check(rc, "psalm_mask_unpack_bits")
+        return out
+
+    def mask_pair_counts(self, bits_a, bits_b=None, out=None):
+        """bits_a (ma,nw), bits_b (mb,nw) int64 bit planes (default: a against itself) -> inter (ma,mb) i32 = popcount(a_i & b_j) over the words,
+        1 <= ma, mb <= 1024: psalm_mask_pair_counts.  `out` may be given; the call zeroes it itself."""
+        self._want_bits(bits_a, "mask_pair_counts")
+        bits_b = bits_a if bits_b is None else self._want_bits(bits_b, "mask_pair_counts")
+        (ma, nw), (mb, nwb) = bits_a.shape, bits_b.shape
+        if nw != nwb or nw < 1:
+            raise PsalmHipError(f"mask_pair_counts: bit rows of {nw} and {nwb} words")
+        if not (1 <= ma <= self.MASK_PAIRS_MAX and 1 <= mb <= self.MASK_PAIRS_MAX):
+            raise PsalmHipError(f"mask_pair_counts: {ma} x {mb} planes (1..{self.MASK_PAIRS_MAX} per side)")
+        inter = self.empty(ma, mb, dtype=torch.int32) if out is None else self._want(out, torch.int32, (ma, mb), "mask_pair_counts out")
+        rc = self.lib.psalm_mask_pair_counts(self._p(bits_a), ma, self._p(bits_b), mb, c_long(nw), self._p(inter), self._stream())
+        self._check(rc, "psalm_mask_pair_counts")
+        return inter
+
+    def mask_nms(self, inter, areas, scores, thr_num, thr_den, min_area=1, min_score=None, out_kept=None, out_keep=None, out_owner=None):
+        """Greedy NMS on inter (m,m) i32, areas (m) i32, scores (m) f32 (NaN-free), 1 <= m <= 1024, under IoU > thr_num / thr_den (exact, strict;
+        0 < thr_num <= thr_den <= 4096): psalm_mask_nms.  Descending score, equal scores the lowest index first; min_area / min_score filter
+        (min_score=None: no score filter).  -> (kept (m + 1) i32 = [K, the K kept indices in rank order, -1 ...], keep (m) i32 = 1 kept / 0
+        suppressed / -1 filtered, owner (m) i32 = the kept candidate standing for each, -1 if filtered)."""
+        if not torch.is_tensor(inter) or inter.dim() != 2 or inter.shape[0] != inter.shape[1]:
+            raise PsalmHipError(f"mask_nms: inter (m,m) int32, got {tuple(getattr(inter, 'shape', ()))}")
+        m = int(inter.shape[0])
+        if not 1 <= m <= self.MASK_PAIRS_MAX:
+            raise PsalmHipError(f"mask_nms: {m} candidates (1..{self.MASK_PAIRS_MAX})")
+        self._want(inter, torch.int32, (m, m), "mask_nms inter")
+        self._want(areas, torch.int32, (m,), "mask_nms areas")
+        self._want(scores, torch.float32, (m,), "mask_nms scores")
+        thr_num, thr_den = int(thr_num), int(thr_den)
+        if not (0 < thr_num <= thr_den <= 4096):
+            raise PsalmHipError(f"mask_nms: threshold {thr_num}/{thr_den} (0 < thr_num <= thr_den <= 4096)")
+        kept = self.empty(m + 1, dtype=torch.int32) if out_kept is None else self._want(out_kept, torch.int32, (m + 1,), "mask_nms out_kept")
+        keep = self.empty(m, dtype=torch.int32) if out_keep is None else self._want(out_keep, torch.int32, (m,), "mask_nms out_keep")
+        owner = self.empty(m, dtype=torch.int32) if out_owner is None else self._want(out_owner, torch.int32, (m,), "mask_nms out_owner")
+        ms = float("-inf") if min_score is None else float(min_score)
+        rc = self.lib.psalm_mask_nms(self._p(inter), self._p(areas), self._p(scores), m, thr_num, thr_den, int(min_area), c_float(ms), self._p(kept),
+                                     self._p(keep), self._p(owner), self._stream())
+        self._check(rc, "psalm_mask_nms")
+        return kept, keep, owner
+
+    def mask_paint_bits(self, bits, kept, shape, out=None):
+        """bits (m,nw) int64, kept (m + 1) i32 as psalm_mask_nms writes it (K read on the device), shape = (H, W) (or HW) -> labels (H,W) i32:
+        1 + the first k < K whose bit row kept[1 + k] holds the pixel, 0 for none: psalm_mask_paint_bits."""
+        self._want_bits(bits, "mask_paint_bits")
+        dims = tuple(int(v) for v in shape) if isinstance(shape, (tuple, list)) else (int(shape),)
+        HW = int(np.prod(dims))
+        m, nw = bits.shape
+        if self.mask_bits_words(HW) != nw:
+            raise PsalmHipError(f"mask_paint_bits: planes of {HW} pixels have {self.mask_bits_words(HW)} words, the bit rows have {nw}")
+        if not 1 <= m <= self.MASK_PAIRS_MAX:
+            raise PsalmHipError(f"mask_paint_bits: {m} bit rows (1..{self.MASK_PAIRS_MAX})")
+        self._want(kept, torch.int32, (m + 1,), "mask_paint_bits kept")
+        labels = self.empty(*dims, dtype=torch.int32) if out is None else self._want(out, torch.int32, dims, "mask_paint_bits out")
+        rc = self.lib.psalm_mask_paint_bits(self._p(bits), c_long(nw), self._p(kept), m, c_long(HW), self._p(labels), self._stream())
+        self._check(rc, "psalm_mask_paint_bits")
+        return labels
 
 
 _OPS: Optional[Ops] = None

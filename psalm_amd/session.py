@@ -713,3 +713,102 @@ class SessionMixin:
                 outs.append(res)
             results.append(outs)
         return results
+
+    @torch.no_grad()
+    def segment_everything(self, session: "ImageSession", input_ids, attention_mask=None, *, grid=(8, 8), regions=None, radius=None,
+                           iou_thr=0.7, min_area: int = 1, min_score: Optional[float] = None,
+                           region_index_sampler: Callable = default_region_index_sampler):
+        """"Show me all the objects": a grid of clicks on the session's image, one mask per object back.  `input_ids` (N, T): region-task prompts
+        on the session's image that hold R <region> tokens together, 1 <= R <= 1024.  Either `grid=(gy, gx)` with gy * gx == R -- one click per
+        cell at the cell centre ((2 i + 1) h // (2 gy), (2 j + 1) w // (2 gx)) of the original (h, w), dealt to the prompts in row-major order by
+        their token counts, `radius` overriding the click's radius -- or `regions` in the grammar of `segment(regions=)` (then pass grid=None).
+
+        One call of the pipeline behind `segment(..., regions=..., pick=True)`; then, all on the device: the picked queries' planes of every
+        prompt are packed into ONE (R, nw) bit buffer through the index list (psalm_mask_pack_bits: no byte gather), all-pairs intersections
+        (psalm_mask_pair_counts), greedy NMS (psalm_mask_nms: descending picked score, equal scores the lower click first; a mask of fewer than
+        `min_area` pixels or a score below `min_score` is filtered; a click whose mask's IoU with an already kept one EXCEEDS `iou_thr` --
+        compared as the rational of evalout.iou_fraction, 0.7 = 7/10, strictly -- is suppressed by the first such one) and the label map
+        (psalm_mask_paint_bits).  ONE read-back, the kept block; then the K survivors are unpacked (psalm_mask_unpack_bits) and boxed
+        (psalm_mask_boxes, whatever the `mask_boxes` switch says).
+
+        Returns device tensors, survivors by descending score: `masks` (K, H, W) uint8, `scores` (K) float32, `queries` (K) int64, `regions` (K)
+        int64 (the click behind each survivor, flat over the prompts), `areas` (K) int32, `boxes` (K, 4) float32 (the `mask_boxes` convention),
+        `labels` (H, W) int32 (0: background, k + 1: survivor k; the better score wins a contested pixel), `owner` (R) int64 (per click the click
+        whose mask stands for it, -1: filtered), `keep` (R) int32 (1 kept, 0 suppressed, -1 filtered), `prompts` (what `segment` returned)."""
+        from .evalout import iou_fraction
+        if self.seg_task != "region":
+            raise ValueError(f"segment_everything: clicks are prompts of the region task (this model's seg_task = {self.seg_task!r})")
+        if not isinstance(session, ImageSession) or session.model is not self:
+            raise ValueError("segment_everything: this session was made by another model (or replica)")
+        try:
+            num, den = iou_fraction(iou_thr)
+        except ValueError as e:
+            raise ValueError(f"segment_everything: {e}") from None
+        ids = input_ids[None] if input_ids.dim() == 1 else input_ids
+        n_tok = (ids == REGION_TOKEN_INDEX).sum(1).tolist()
+        R = int(sum(n_tok))
+        if not 1 <= R <= 1024:
+            raise ValueError(f"segment_everything: the prompts hold {R} <region> tokens (1..1024)")
+        if (grid is None) == (regions is None):
+            raise ValueError("segment_everything: give either `grid` or `regions` (with `regions`, pass grid=None)")
+        if grid is not None:
+            ok = isinstance(grid, (tuple, list)) and len(grid) == 2 and all(
+                isinstance(v, (int, np.integer)) and not isinstance(v, (bool, np.bool_)) and v >= 1 for v in grid)
+            if not ok or int(grid[0]) * int(grid[1]) != R:
+                raise ValueError(f"segment_everything: grid {grid!r} for {R} <region> tokens (gy * gx must equal their number)")
+            tr = session.seg_info.get("transforms") if isinstance(session.seg_info, dict) else None
+            if tr is None:
+                raise ValueError("segment_everything: regions need the session's seg_info['transforms'] (the resize / pad record of the image: "
+                                 "encode_image(images, seg_info))")
+            h, w = int(tr["resize"][0]), int(tr["resize"][1])
+            gy, gx = int(grid[0]), int(grid[1])
+            extra = {} if radius is None else {"radius": radius}
+            clicks = [dict(points=[((2 * i + 1) * h // (2 * gy), (2 * j + 1) * w // (2 * gx))], **extra) for i in range(gy) for j in range(gx)]
+            regions, g0 = [], 0
+            for k in n_tok:
+                regions.append(clicks[g0:g0 + k])
+                g0 += k
+        elif radius is not None:
+            raise ValueError("segment_everything: `radius` overrides the radius of the grid's clicks; with `regions`, give it per region prompt")
+        kw = dict(input_ids=input_ids, attention_mask=attention_mask, regions=regions)
+        prompts = self._segment_requests([(session, kw)], grouped=False, postprocess=True, stages=None,
+                                         region_point_sampler=default_region_point_sampler, region_index_sampler=region_index_sampler, pick=True)[0]
+        out = self._everything_dedup(prompts, n_tok, num, den, min_area, min_score)
+        out["prompts"] = prompts
+        return out
+
+    def _everything_dedup(self, prompts, n_tok, num, den, min_area, min_score):
+        """The device step behind the pipeline: `prompts`, what `segment(..., pick=True)` returned for prompts of n_tok[b] regions each ->
+        segment_everything's result without "prompts".  Reads `instances.pred_masks`, `picked_query` and `picked_scores` of every prompt."""
+        o = self.ops
+        R = int(sum(n_tok))
+        sizes = {tuple(p["instances"].pred_masks.shape[1:]) for p in prompts}
+        if len(sizes) != 1:
+            raise ValueError(f"segment_everything: the prompts produced masks of different sizes {sorted(sizes)}")
+        Hh, Ww = sizes.pop()
+        bits = o.empty(R, o.mask_bits_words(Hh * Ww), dtype=torch.int64)
+        areas = o.empty(R, dtype=torch.int32)
+        g0 = 0
+        for k, p in zip(n_tok, prompts):                          # the picked queries' planes, prompt by prompt, into rows g0 .. g0 + k of the one buffer
+            if k:
+                planes = p["instances"].pred_masks
+                o.mask_pack_bits(planes if planes.is_contiguous() else planes.contiguous(), index=p["picked_query"].to(torch.int32),
+                                 out_bits=bits[g0:g0 + k], out_areas=areas[g0:g0 + k])
+                g0 += k
+        with_regions = [p for k, p in zip(n_tok, prompts) if k]
+        scores = with_regions[0]["picked_scores"] if len(with_regions) == 1 else torch.cat([p["picked_scores"] for p in with_regions])
+        queries = with_regions[0]["picked_query"] if len(with_regions) == 1 else torch.cat([p["picked_query"] for p in with_regions])
+        inter = o.mask_pair_counts(bits)
+        kept, keep, owner = o.mask_nms(inter, areas, scores.contiguous(), num, den, min_area=min_area, min_score=min_score)
+        labels = o.mask_paint_bits(bits, kept, (Hh, Ww))
+        K = int(kept.cpu()[0])                                    # the one read-back
+        if K:
+            rows = kept[1:1 + K]
+            masks = o.mask_unpack_bits(bits, (Hh, Ww), rows=rows)
+            boxes, kept_areas = o.mask_boxes(masks)
+            which = o.to_i64(rows)
+        else:
+            masks = o.empty(0, Hh, Ww, dtype=torch.uint8)
+            boxes, kept_areas, which = o.empty(0, 4), o.empty(0, dtype=torch.int32), o.empty(0, dtype=torch.int64)
+        return {"masks": masks, "scores": scores[which], "queries": queries[which], "regions": which, "areas": kept_areas, "boxes": boxes,
+                "labels": labels, "owner": o.to_i64(owner), "keep": keep}
