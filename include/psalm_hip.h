@@ -41,8 +41,9 @@ const char* psalm_last_error(void);
  * 12: region prompts of image sessions: psalm_mask_rasterize, psalm_mask_dilate_disc, psalm_region_best, psalm_mask_gather_u8.
  * 13: boxes and areas from masks: psalm_mask_boxes (+ _workspace), psalm_label_boxes.
  * 14: all-pairs mask overlap on bit planes: psalm_mask_bits_words, psalm_mask_pack_bits, psalm_mask_unpack_bits, psalm_mask_pair_counts,
- *    psalm_mask_nms, psalm_mask_paint_bits. */
-#define PSALM_ABI_VERSION 14
+ *    psalm_mask_nms, psalm_mask_paint_bits.
+ * 15: connected components of binary planes: psalm_mask_components (+ _workspace), psalm_mask_clean (+ _workspace). */
+#define PSALM_ABI_VERSION 15
 int psalm_abi_version(void);
 const char* psalm_backend(void); /* "hip-gfx950" */
 
@@ -827,6 +828,40 @@ int psalm_mask_nms(const int* inter, const int* areas, const float* scores, int 
  * a contested pixel.  K = kept[0] is read on the device (no host synchronisation in front of this call); m <= 1024, the number of bit rows, bounds K and the
  * entries (one outside [0, m) is passed over). */
 int psalm_mask_paint_bits(const unsigned long long* bits, long nw, const int* kept, int m, long HW, int* labels, void* stream);
+
+/* ------------------------------------------------------------------------------------------------------------------
+ * Connected components of binary planes (csrc/components.hip; psalm_amd/evalout.py mask_components / clean_masks, PSALM.segment_everything(
+ * min_island=, max_hole=)): remove regions below N pixels, fill holes below N pixels, split a mask into its parts.  Inputs follow psalm_mask_boxes:
+ * masks (n,H,W) contiguous, float32 (dtype_is_u8 = 0; set when f > 0: NaN, -0.0 and negatives are not) or bytes (1; set when != 0); output row i is
+ * plane index_dev[i] (m entries, int32 on the device; an entry outside [0, n) is the EMPTY plane), or plane i when index_dev is NULL (then m must
+ * equal n).  H * W < 2^31, m <= 65535, m == 0 is a no-op; planes need no alignment beyond the element's own.  All results are integers combined
+ * with integer min / max / add atomics: exact, independent of the order of arrival, so two calls give the same bytes.  Nothing allocates or
+ * synchronises; what a call accumulates into it zeroes itself (memset nodes on `stream`).  Separate launches: tile-local union-find in LDS
+ * (32 x 32 tiles), a lock-free merge across tile edges, a flattening pass with per-root area / border flag, a two-level scan that numbers the roots. */
+/* connectivity 4 | 8 (anything else: an error code); invert 0 | 1: with 1 the UNSET pixels are the labelled class.
+ *   labels (m,H,W) i32: every pixel of the labelled class gets 1 + the rank of its component among the plane's components ordered by their lowest
+ *          row-major pixel index (the numbering of scipy.ndimage.label); every other pixel 0.
+ *   count (m) i32:     the number of components of each plane.
+ *   table (m,max_comp,6) i32 or NULL, zeroed by the call: row k - 1 = [x0, y0, x1, y1, area, border] of component k <= max_comp -- the box in
+ *          psalm_label_boxes' convention (x1, y1 exclusive), border = 1 when the component holds a pixel of the first or last row or column.
+ *          Components beyond max_comp are still labelled and counted, only not tabled.  1 <= max_comp <= 65536.
+ * workspace: psalm_mask_components_workspace(m, H, W) bytes (-1: bad arguments), 4-byte aligned: three int32 planes per output row and the
+ * scan's block sums. */
+long psalm_mask_components_workspace(int m, int H, int W);
+int psalm_mask_components(const void* masks, int dtype_is_u8, int n, int H, int W, const int* index_dev, int m, int connectivity, int invert,
+                          int* labels, int* count, int* table, int max_comp, void* workspace, long workspace_bytes, void* stream);
+/* Cleanup per plane, in this order (the order of SAM's post-processing: a ring whose hole is filled is then judged as the blob it became):
+ *   1 holes, if max_hole > 0: the components of the UNSET pixels under the complementary connectivity (4 when `connectivity` is 8, 8 when it
+ *     is 4); one that holds no pixel of the first or last row or column and has at most max_hole pixels becomes set;
+ *   2 islands, if min_island > 0: the components of the set pixels of step 1's result under `connectivity`; one with fewer than min_island
+ *     pixels is cleared.  A plane may become empty: there is no keep-the-largest exception.
+ * out (m,H,W) bytes of 0 / 1; areas (m) i32 = set pixels of the cleaned planes; filled / removed (m) i32 = pixels changed by step 1 / step 2.
+ * min_island, max_hole >= 0; a step whose parameter is 0 launches no labelling, with both 0 the call is a binarising gather.
+ * workspace: psalm_mask_clean_workspace(m, H, W) bytes (-1: bad arguments), 4-byte aligned (three int32 planes per output row); may be NULL when
+ * both parameters are 0. */
+long psalm_mask_clean_workspace(int m, int H, int W);
+int psalm_mask_clean(const void* masks, int dtype_is_u8, int n, int H, int W, const int* index_dev, int m, int connectivity, int min_island,
+                     int max_hole, unsigned char* out, int* areas, int* filled, int* removed, void* workspace, long workspace_bytes, void* stream);
 
 #ifdef __cplusplus
 }

@@ -16,6 +16,8 @@ with one tiny RCCL all-reduce (`psalm_amd.dist.reduce_metrics`, the role of Aver
     mask_boxes(masks) / label_boxes(labels, n)    llava_phi.py:319,395,438-440 (the commented-out `BitMasks(..).get_bounding_boxes()`) -> boxes, areas
     mask_pair_counts(masks_a, masks_b)            COCO mask matching / DAVIS J: the prediction x ground-truth overlap matrix on bit planes
     mask_nms(masks, scores, iou_thr)              greedy mask NMS under an exact rational IoU threshold (PSALM.segment_everything's rule)
+    mask_components(masks, connectivity)          a mask's connected parts as instances: labels in scipy.ndimage.label's numbering, count, box / area table
+    clean_masks(masks, min_island, max_hole)      SAM-style post-processing: fill holes up to N pixels, then drop islands below N pixels
     coco_instance_records(instances, image_id)    detectron2 instances_to_coco_json (instance_evaluation.py) -> the COCO result records
 """
 from __future__ import annotations
@@ -269,6 +271,38 @@ def mask_nms(masks: torch.Tensor, scores: torch.Tensor, iou_thr=0.7, min_area: i
     K = int(kept.cpu()[0])                                            # the one read-back
     kept = o.to_i64(kept[1:1 + K]) if K else torch.empty(0, dtype=torch.int64, device=o.device)
     return {"kept": kept, "keep": keep, "owner": owner, "areas": areas, "inter": inter}
+
+
+def _planes(o, masks, what):
+    if not torch.is_tensor(masks) or masks.dim() != 3:
+        raise H.PsalmHipError(f"{what}: (n,H,W) float32 / uint8 / bool masks")
+    masks = _on_device(o, masks, (torch.float32, torch.uint8, torch.bool), what)
+    if masks.shape[0] > 65535:
+        raise H.PsalmHipError(f"{what}: {masks.shape[0]} masks (at most 65535)")
+    return masks
+
+
+def mask_components(masks: torch.Tensor, connectivity: int = 8, max_components: int = 256, ops=None) -> dict:
+    """A mask's connected parts as instances -- a referring or semantic mask that covers three separate objects is three components: masks
+    (n,H,W) float32 (set: > 0) | uint8 | bool (set: != 0), up to 65535 of them, on host or device -> {"labels": (n,H,W) int32, 0 off the mask and
+    1 + rank on it, the plane's components ranked by their lowest row-major pixel (the numbering of scipy.ndimage.label, structure = the full
+    3 x 3 for connectivity 8, the cross for 4); "count": (n) int32; "table": (n, max_components, 6) int32 = [x0, y0, x1, y1, area, border] per
+    component (the box convention of `label_boxes`; border = 1 when it touches the image border; zeros beyond `count`; components beyond
+    max_components are labelled and counted, not tabled)}, on the device.  Nothing is read back."""
+    o = _ops(ops)
+    labels, count, table = o.mask_components(_planes(o, masks, "mask_components"), connectivity=connectivity, max_components=max_components)
+    return {"labels": labels, "count": count, "table": table}
+
+
+def clean_masks(masks: torch.Tensor, min_island: int = 0, max_hole: int = 0, connectivity: int = 8, ops=None) -> dict:
+    """What every click-to-mask tool does to its results: masks (n,H,W) float32 (set: > 0) | uint8 | bool, up to 65535, on host or device ->
+    {"masks": (n,H,W) uint8 of 0 / 1, "areas": (n) int32 of the cleaned masks, "removed": (n) int32, "filled": (n) int32 pixels changed}, on the
+    device.  First the holes -- components of the unset pixels, under the complementary connectivity, that do not touch the image border -- of
+    at most `max_hole` pixels are filled; then the components of the set pixels with fewer than `min_island` pixels are dropped (a ring whose
+    hole was filled is judged as the blob it became; a mask may become empty).  A parameter of 0 skips its step.  Nothing is read back."""
+    o = _ops(ops)
+    out, areas, filled, removed = o.mask_clean(_planes(o, masks, "clean_masks"), connectivity=connectivity, min_island=min_island, max_hole=max_hole)
+    return {"masks": out, "areas": areas, "removed": removed, "filled": filled}
 
 
 def coco_instance_records(instances, image_id, category_ids: Optional[Sequence[int]] = None, ops=None) -> List[dict]:

@@ -49,7 +49,7 @@ def _dt(t: torch.Tensor) -> int:
         raise PsalmHipError(f"unsupported dtype {t.dtype} (float32 / bfloat16 only)")
 
 
-ABI_VERSION = 14       # == PSALM_ABI_VERSION of include/psalm_hip.h (tests/test_0_abi.py compares the two and the built library's answer)
+ABI_VERSION = 15       # == PSALM_ABI_VERSION of include/psalm_hip.h (tests/test_0_abi.py compares the two and the built library's answer)
 
 
 class _ProfiledLib:
@@ -1992,6 +1992,105 @@ class Ops:
         rc = self.lib.psalm_mask_paint_bits(self._p(bits), c_long(nw), self._p(kept), m, c_long(HW), self._p(labels), self._stream())
         self._check(rc, "psalm_mask_paint_bits")
         return labels
+
+    # ------------------------------------------------------------------ connected components of binary planes (csrc/components.hip)
+    COMPONENTS_WS_BYTES = 256 << 20
+
+    def _planes_args(self, masks, index, connectivity, what):
+        if not torch.is_tensor(masks) or masks.dim() != 3 or masks.dtype not in (torch.float32, torch.uint8, torch.bool):
+            raise PsalmHipError(f"{what}: masks (n,H,W) float32 / uint8 / bool, got {getattr(masks, 'dtype', type(masks))} "
+                                f"{tuple(getattr(masks, 'shape', ()))}")
+        if masks.dtype == torch.bool:
+            masks = masks.view(torch.uint8)
+        if connectivity not in (4, 8) or isinstance(connectivity, bool):
+            raise PsalmHipError(f"{what}: connectivity {connectivity!r} (4 or 8)")
+        n, Hh, Ww = (int(v) for v in masks.shape)
+        if Hh * Ww >= 1 << 31:
+            raise PsalmHipError(f"{what}: planes of {Hh} x {Ww} pixels (H * W < 2^31)")
+        m = n if index is None else int(index.numel())
+        if index is not None:
+            self._want(index, torch.int32, (m,), f"{what} index")
+        if m > 65535:
+            raise PsalmHipError(f"{what}: {m} output rows (at most 65535)")
+        return masks, n, Hh, Ww, m
+
+    def _plane_chunks(self, fn, m, Hh, Ww, max_workspace_bytes, what):
+        """[(first row, rows, workspace bytes)]: the m output rows in chunks whose workspace stays under max_workspace_bytes (at least one row)"""
+        max_ws = self.COMPONENTS_WS_BYTES if max_workspace_bytes is None else int(max_workspace_bytes)
+        if max_ws < 0:
+            raise PsalmHipError(f"{what}: max_workspace_bytes = {max_ws}")
+        fn.restype = c_long
+        one = int(fn(1, Hh, Ww))
+        if one < 0:
+            raise PsalmHipError(f"{what}: planes of {Hh} x {Ww} pixels (H * W < 2^31)")
+        per = max(1, min(m, max_ws // one if one else m))
+        return [(r0, min(per, m - r0), int(fn(min(per, m - r0), Hh, Ww))) for r0 in range(0, m, per)]
+
+    def mask_components(self, masks, index=None, connectivity=8, invert=False, max_components=256, want_table=True, max_workspace_bytes=None):
+        """masks (n,H,W) float32 (set: > 0) | uint8 / bool (set: != 0) -> (labels (m,H,W) i32: 1 + the rank of the pixel's component among the plane's
+        components ordered by their lowest row-major pixel, 0 for the other class; count (m) i32; table (m,max_components,6) i32 of [x0, y0, x1, y1,
+        area, border] per component, None with want_table=False): psalm_mask_components.  index (m) i32 on the device: the planes to label (an entry
+        outside [0, n) is the empty plane), default all n in order; invert: label the unset pixels.  The rows are walked in chunks whose workspace
+        (three int32 planes per row) stays under max_workspace_bytes (default 256 MiB; at least one row per chunk): the result does not depend on it."""
+        masks, n, Hh, Ww, m = self._planes_args(masks, index, connectivity, "mask_components")
+        max_comp = int(max_components)
+        if want_table and not 1 <= max_comp <= 65536:
+            raise PsalmHipError(f"mask_components: max_components = {max_components} (1..65536)")
+        labels = self.empty(m, Hh, Ww, dtype=torch.int32)
+        count = self.empty(m, dtype=torch.int32)
+        table = self.empty(m, max_comp, 6, dtype=torch.int32) if want_table else None
+        if m == 0:
+            return labels, count, table
+        chunks = self._plane_chunks(self.lib.psalm_mask_components_workspace, m, Hh, Ww, max_workspace_bytes, "mask_components")
+        if index is None and len(chunks) > 1:
+            index = self._iota(n)                                     # a chunk of rows is a piece of the index list
+        for r0, k, nbytes in chunks:
+            ws = self._stage_ws("mask_components", max(nbytes, 4))
+            rc = self.lib.psalm_mask_components(self._p(masks), 1 if masks.dtype == torch.uint8 else 0, n, Hh, Ww,
+                                                self._p(index[r0:r0 + k]) if index is not None else c_void_p(0), k,
+                                                int(connectivity), 1 if invert else 0, self._p(labels[r0:r0 + k]), self._p(count[r0:r0 + k]),
+                                                self._p(table[r0:r0 + k]) if want_table else c_void_p(0), max_comp if want_table else 1,
+                                                self._p(ws), c_long(nbytes), self._stream())
+            self._check(rc, "psalm_mask_components")
+        return labels, count, table
+
+    def mask_clean(self, masks, index=None, connectivity=8, min_island=0, max_hole=0, out=None, out_areas=None, out_filled=None, out_removed=None,
+                   max_workspace_bytes=None):
+        """masks (n,H,W) float32 (set: > 0) | uint8 / bool (set: != 0) -> (out (m,H,W) u8 of 0 / 1, areas (m) i32 of the cleaned planes, filled (m)
+        i32, removed (m) i32): psalm_mask_clean.  First the holes -- components of the unset pixels under the complementary connectivity that miss
+        the image border -- of at most max_hole pixels become set, then the islands of fewer than min_island pixels are cleared; a parameter of 0
+        skips its step.  index (m) i32 on the device as in mask_components; the outputs may be given (views of a caller-owned block); chunked as
+        mask_components."""
+        masks, n, Hh, Ww, m = self._planes_args(masks, index, connectivity, "mask_clean")
+        min_island, max_hole = int(min_island), int(max_hole)
+        if min_island < 0 or max_hole < 0:
+            raise PsalmHipError(f"mask_clean: min_island = {min_island}, max_hole = {max_hole} (both >= 0)")
+        out = self.empty(m, Hh, Ww, dtype=torch.uint8) if out is None else self._want(out, torch.uint8, (m, Hh, Ww), "mask_clean out")
+        areas = self.empty(m, dtype=torch.int32) if out_areas is None else self._want(out_areas, torch.int32, (m,), "mask_clean out_areas")
+        filled = self.empty(m, dtype=torch.int32) if out_filled is None else self._want(out_filled, torch.int32, (m,), "mask_clean out_filled")
+        removed = self.empty(m, dtype=torch.int32) if out_removed is None else self._want(out_removed, torch.int32, (m,), "mask_clean out_removed")
+        if m == 0:
+            return out, areas, filled, removed
+        labelling = min_island > 0 or max_hole > 0
+        chunks = self._plane_chunks(self.lib.psalm_mask_clean_workspace, m, Hh, Ww, max_workspace_bytes, "mask_clean") if labelling else [(0, m, 0)]
+        if index is None and len(chunks) > 1:
+            index = self._iota(n)
+        for r0, k, nbytes in chunks:
+            ws = self._stage_ws("mask_components", max(nbytes, 4)) if labelling else None
+            rc = self.lib.psalm_mask_clean(self._p(masks), 1 if masks.dtype == torch.uint8 else 0, n, Hh, Ww,
+                                           self._p(index[r0:r0 + k]) if index is not None else c_void_p(0), k, int(connectivity), min_island, max_hole,
+                                           self._p(out[r0:r0 + k]), self._p(areas[r0:r0 + k]), self._p(filled[r0:r0 + k]), self._p(removed[r0:r0 + k]),
+                                           self._p(ws), c_long(nbytes), self._stream())
+            self._check(rc, "psalm_mask_clean")
+        return out, areas, filled, removed
+
+    def _iota(self, n):
+        """0 .. n - 1 as int32 on the device (cached per length)"""
+        key = ("iota", n)
+        t = self._ws.get(key)
+        if t is None:
+            t = self._ws[key] = torch.arange(n, dtype=torch.int32).to(self.device)
+        return t
 
 
 _OPS: Optional[Ops] = None

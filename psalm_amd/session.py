@@ -717,7 +717,8 @@ class SessionMixin:
     @torch.no_grad()
     def segment_everything(self, session: "ImageSession", input_ids, attention_mask=None, *, grid=(8, 8), regions=None, radius=None,
                            iou_thr=0.7, min_area: int = 1, min_score: Optional[float] = None,
-                           region_index_sampler: Callable = default_region_index_sampler):
+                           region_index_sampler: Callable = default_region_index_sampler, min_island: int = 0, max_hole: int = 0,
+                           connectivity: int = 8):
         """"Show me all the objects": a grid of clicks on the session's image, one mask per object back.  `input_ids` (N, T): region-task prompts
         on the session's image that hold R <region> tokens together, 1 <= R <= 1024.  Either `grid=(gy, gx)` with gy * gx == R -- one click per
         cell at the cell centre ((2 i + 1) h // (2 gy), (2 j + 1) w // (2 gx)) of the original (h, w), dealt to the prompts in row-major order by
@@ -734,7 +735,13 @@ class SessionMixin:
         Returns device tensors, survivors by descending score: `masks` (K, H, W) uint8, `scores` (K) float32, `queries` (K) int64, `regions` (K)
         int64 (the click behind each survivor, flat over the prompts), `areas` (K) int32, `boxes` (K, 4) float32 (the `mask_boxes` convention),
         `labels` (H, W) int32 (0: background, k + 1: survivor k; the better score wins a contested pixel), `owner` (R) int64 (per click the click
-        whose mask stands for it, -1: filtered), `keep` (R) int32 (1 kept, 0 suppressed, -1 filtered), `prompts` (what `segment` returned)."""
+        whose mask stands for it, -1: filtered), `keep` (R) int32 (1 kept, 0 suppressed, -1 filtered), `prompts` (what `segment` returned).
+
+        `min_island` / `max_hole` > 0 clean every click's picked mask first (psalm_mask_clean: holes of at most max_hole pixels, judged under the
+        complementary connectivity, are filled; then islands of fewer than min_island pixels under `connectivity` are dropped) and everything
+        above -- pair counts, NMS with `min_area` on the cleaned area, the label map, `masks`, `areas`, `boxes` -- describes the cleaned masks;
+        the result gains `cleaned` (R, 2) int32 = [removed, filled] pixels per click.  With both 0 the call is launch for launch the one
+        without them."""
         from .evalout import iou_fraction
         if self.seg_task != "region":
             raise ValueError(f"segment_everything: clicks are prompts of the region task (this model's seg_task = {self.seg_task!r})")
@@ -744,6 +751,11 @@ class SessionMixin:
             num, den = iou_fraction(iou_thr)
         except ValueError as e:
             raise ValueError(f"segment_everything: {e}") from None
+        for name, v in (("min_island", min_island), ("max_hole", max_hole)):
+            if isinstance(v, (bool, np.bool_)) or not isinstance(v, (int, np.integer)) or v < 0:
+                raise ValueError(f"segment_everything: {name} = {v!r} (an integer >= 0)")
+        if isinstance(connectivity, (bool, np.bool_)) or connectivity not in (4, 8):
+            raise ValueError(f"segment_everything: connectivity = {connectivity!r} (4 or 8)")
         ids = input_ids[None] if input_ids.dim() == 1 else input_ids
         n_tok = (ids == REGION_TOKEN_INDEX).sum(1).tolist()
         R = int(sum(n_tok))
@@ -773,13 +785,14 @@ class SessionMixin:
         kw = dict(input_ids=input_ids, attention_mask=attention_mask, regions=regions)
         prompts = self._segment_requests([(session, kw)], grouped=False, postprocess=True, stages=None,
                                          region_point_sampler=default_region_point_sampler, region_index_sampler=region_index_sampler, pick=True)[0]
-        out = self._everything_dedup(prompts, n_tok, num, den, min_area, min_score)
+        out = self._everything_dedup(prompts, n_tok, num, den, min_area, min_score, int(min_island), int(max_hole), int(connectivity))
         out["prompts"] = prompts
         return out
 
-    def _everything_dedup(self, prompts, n_tok, num, den, min_area, min_score):
+    def _everything_dedup(self, prompts, n_tok, num, den, min_area, min_score, min_island=0, max_hole=0, connectivity=8):
         """The device step behind the pipeline: `prompts`, what `segment(..., pick=True)` returned for prompts of n_tok[b] regions each ->
-        segment_everything's result without "prompts".  Reads `instances.pred_masks`, `picked_query` and `picked_scores` of every prompt."""
+        segment_everything's result without "prompts".  Reads `instances.pred_masks`, `picked_query` and `picked_scores` of every prompt.
+        min_island / max_hole > 0: the picked planes are cleaned (psalm_mask_clean) into one (R, H, W) byte buffer, which is packed instead."""
         o = self.ops
         R = int(sum(n_tok))
         sizes = {tuple(p["instances"].pred_masks.shape[1:]) for p in prompts}
@@ -788,13 +801,24 @@ class SessionMixin:
         Hh, Ww = sizes.pop()
         bits = o.empty(R, o.mask_bits_words(Hh * Ww), dtype=torch.int64)
         areas = o.empty(R, dtype=torch.int32)
+        clean = min_island > 0 or max_hole > 0
+        if clean:
+            cleaned_planes = o.empty(R, Hh, Ww, dtype=torch.uint8)
+            cleaned = o.empty(2, R, dtype=torch.int32)             # rows: removed, filled
         g0 = 0
         for k, p in zip(n_tok, prompts):                          # the picked queries' planes, prompt by prompt, into rows g0 .. g0 + k of the one buffer
             if k:
                 planes = p["instances"].pred_masks
-                o.mask_pack_bits(planes if planes.is_contiguous() else planes.contiguous(), index=p["picked_query"].to(torch.int32),
-                                 out_bits=bits[g0:g0 + k], out_areas=areas[g0:g0 + k])
+                planes = planes if planes.is_contiguous() else planes.contiguous()
+                if clean:
+                    o.mask_clean(planes, index=p["picked_query"].to(torch.int32), connectivity=connectivity, min_island=min_island, max_hole=max_hole,
+                                 out=cleaned_planes[g0:g0 + k], out_areas=areas[g0:g0 + k], out_filled=cleaned[1, g0:g0 + k],
+                                 out_removed=cleaned[0, g0:g0 + k])
+                else:
+                    o.mask_pack_bits(planes, index=p["picked_query"].to(torch.int32), out_bits=bits[g0:g0 + k], out_areas=areas[g0:g0 + k])
                 g0 += k
+        if clean:
+            o.mask_pack_bits(cleaned_planes, out_bits=bits, want_areas=False)      # the areas are those of the cleaned planes already
         with_regions = [p for k, p in zip(n_tok, prompts) if k]
         scores = with_regions[0]["picked_scores"] if len(with_regions) == 1 else torch.cat([p["picked_scores"] for p in with_regions])
         queries = with_regions[0]["picked_query"] if len(with_regions) == 1 else torch.cat([p["picked_query"] for p in with_regions])
@@ -810,5 +834,8 @@ class SessionMixin:
         else:
             masks = o.empty(0, Hh, Ww, dtype=torch.uint8)
             boxes, kept_areas, which = o.empty(0, 4), o.empty(0, dtype=torch.int32), o.empty(0, dtype=torch.int64)
-        return {"masks": masks, "scores": scores[which], "queries": queries[which], "regions": which, "areas": kept_areas, "boxes": boxes,
-                "labels": labels, "owner": o.to_i64(owner), "keep": keep}
+        out = {"masks": masks, "scores": scores[which], "queries": queries[which], "regions": which, "areas": kept_areas, "boxes": boxes,
+               "labels": labels, "owner": o.to_i64(owner), "keep": keep}
+        if clean:
+            out["cleaned"] = cleaned.t().contiguous()
+        return out
