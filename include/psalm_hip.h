@@ -42,8 +42,10 @@ const char* psalm_last_error(void);
  * 13: boxes and areas from masks: psalm_mask_boxes (+ _workspace), psalm_label_boxes.
  * 14: all-pairs mask overlap on bit planes: psalm_mask_bits_words, psalm_mask_pack_bits, psalm_mask_unpack_bits, psalm_mask_pair_counts,
  *    psalm_mask_nms, psalm_mask_paint_bits.
- * 15: connected components of binary planes: psalm_mask_components (+ _workspace), psalm_mask_clean (+ _workspace). */
-#define PSALM_ABI_VERSION 15
+ * 15: connected components of binary planes: psalm_mask_components (+ _workspace), psalm_mask_clean (+ _workspace).
+ * 16: RoPE in the [k|v|q|fc1] GEMM's epilogue: psalm_rope_out, psalm_gemm_x3_split_rope, psalm_phi_attention_tables,
+ *    psalm_causal_attention_f32_split_prepared, psalm_phi_forward_plan, PSALM_TUNE_PHI_ROPE_EPILOGUE. */
+#define PSALM_ABI_VERSION 16
 int psalm_abi_version(void);
 const char* psalm_backend(void); /* "hip-gfx950" */
 
@@ -63,13 +65,17 @@ const char* psalm_backend(void); /* "hip-gfx950" */
  *   PSALM_TUNE_MHA_QTILE_WAVES  1 (default): psalm_mha_attention_f32 gives every 16-query tile of a head a wavefront of its own (blocks of
  *                               cdiv(Lq, 16) wavefronts that stage K / V together, double buffered); 0: the r05 kernel, one wavefront that
  *                               walks all query tiles of the head
- *   6..7                        unused */
+ *   PSALM_TUNE_PHI_ROPE_EPILOGUE 1 (default): psalm_phi_forward rotates / scales q and k in the [k|v|q|fc1] GEMM's epilogue (psalm_gemm_x3_split_rope)
+ *                               and builds the key-mask tables once per call (psalm_phi_attention_tables): 4 launches per layer; 0: the RoPE
+ *                               pre-pass in front of every layer's attention kernel (5 launches per layer)
+ *   7                           unused */
 #define PSALM_TUNE_GEMM_XCD_KSPLIT 0
 #define PSALM_TUNE_ATTN_XCD_HEADS 1
 #define PSALM_TUNE_GEMM_MID 2
 #define PSALM_TUNE_DECODER_FUSE 3
 #define PSALM_TUNE_ROW_GROUPS 4
 #define PSALM_TUNE_MHA_QTILE_WAVES 5
+#define PSALM_TUNE_PHI_ROPE_EPILOGUE 6
 #define PSALM_TUNE_COUNT 8
 int psalm_set_tuning(int key, int value);
 int psalm_get_tuning(int key);
@@ -196,6 +202,26 @@ int psalm_gemm_x3_split(const void* A2, long lda, const float* a_scale, const vo
                         const float* bias, void* C, long ldc, int M, int N, int act, int act_col_start, void* split_out, long ld_split,
                         int split_kp, int split_col_off, int split_col_start, int paired, float* split_inv, const float* bound_par,
                         int global_rows, void* workspace, long workspace_bytes, void* stream);
+/* ... whose k and q columns (heads * 64 columns each from k_col / q_col, multiples of 64 below split_col_start) leave the epilogue rotated
+ * (partial RoPE over the first 32 of 64 head dimensions), q also scaled, in the head-major layout the Phi attention kernel reads --
+ * element (row b * L + t, head h, dim d) at ((b * heads + h) * Lp + t) * 64 + d of Qr / Kr, Lp = ceil32(L): what the attention's RoPE pre-pass
+ * writes from C, bit for bit, without the round trip.  The k and q columns are NOT written to C; every other column leaves as
+ * psalm_gemm_x3_split writes it.  Rows t in [L, Lp) of Qr / Kr are not touched (psalm_phi_attention_tables zeroes them).  cos / sin: the
+ * (>= L, 32) tables.  Needs `paired` (every paired form carries the epilogue), M == B * L, L >= 32 when B > 1 (at most one sequence boundary
+ * in a 32-row matrix tile), Qr / Kr below 2 GiB each. */
+typedef struct psalm_rope_out {
+    float* Qr;
+    float* Kr;
+    const float* cos_table;
+    const float* sin_table;
+    int q_col, k_col, heads, B, L, Lp;
+    float scale; /* of q: 1 / sqrt(head_dim) */
+    int pad_;
+} psalm_rope_out;
+int psalm_gemm_x3_split_rope(const void* A2, long lda, const float* a_scale, const void* W2, long ldw, const float* w_scale, int Kp,
+                             const float* bias, void* C, long ldc, int M, int N, int act, int act_col_start, void* split_out, long ld_split,
+                             int split_kp, int split_col_off, int split_col_start, int paired, float* split_inv, const float* bound_par,
+                             int global_rows, const psalm_rope_out* rope, void* workspace, long workspace_bytes, void* stream);
 
 /* Eval-time image pre-processing on the device: replaces detectron2 `T.ResizeShortestEdge` (= Pillow
  * `Image.resize(BILINEAR)` on uint8) + `T.FixedSizeCrop` + `(image - pixel_mean) / pixel_std` of
@@ -258,6 +284,15 @@ int psalm_causal_attention_f32_split(const float* qkv, long ld, int q_off, int k
                                      int split_col_off, const float* split_inv, const float* cos_table, const float* sin_table,
                                      const unsigned char* key_mask, void* workspace, int B, int L, int heads, int head_dim, int rot,
                                      void* stream);
+/* The two steps of psalm_causal_attention_f32_split for callers whose q / k arrive rotated (psalm_gemm_x3_split_rope), on the same workspace
+ * (psalm_causal_attention_f32_workspace: Qr | Kr | Mk | Tk):
+ *   psalm_phi_attention_tables                  once per forward pass: the padded key mask Mk and the per-tile flags Tk from key_mask (B, L), and zeros
+ *                                               in the padding rows [L, ceil32(L)) of Qr / Kr of every head -- nothing else writes those rows
+ *   psalm_causal_attention_f32_split_prepared  the attention kernel alone, on a workspace whose Qr / Kr / Mk / Tk are in place */
+int psalm_phi_attention_tables(const unsigned char* key_mask, void* workspace, int B, int L, int heads, void* stream);
+int psalm_causal_attention_f32_split_prepared(const float* qkv, long ld, int v_off, void* split_out, long ld_split, int split_kp,
+                                              int split_col_off, const float* split_inv, void* workspace, int B, int L, int heads,
+                                              int head_dim, void* stream);
 
 /* Prefix form of the Phi attention (image sessions: one image, N prompts that share their first P rows -- system text + image tokens).  The
  * sequence of prompt n is [P prefix rows | S suffix rows]; only the N * S suffix rows carry queries.  Suffix query s of prompt n attends the P
@@ -523,6 +558,10 @@ long psalm_phi_forward_workspace(const psalm_phi_desc* d, int B, int L);
 int psalm_phi_forward(const psalm_phi_desc* d, const float* embeds, const unsigned char* key_mask, const float* cos_table, const float* sin_table,
                       int B, int L, float* hidden_out, void* workspace, long workspace_bytes, void* gemm_workspace, long gemm_workspace_bytes,
                       void* stream);
+/* The launch sequence psalm_phi_forward issues for (d, B, L) under the current switches: out3 = {1 when q / k are rotated in the [k|v|q|fc1]
+ * GEMM's epilogue (PSALM_TUNE_PHI_ROPE_EPILOGUE; else the RoPE pre-pass runs in front of every layer's attention), launches per layer,
+ * launches in front of the layer loop}.  The epilogue form needs every layer `paired`, 3 * hidden % 256 == 0, L >= 32 when B > 1. */
+int psalm_phi_forward_plan(const psalm_phi_desc* d, int B, int L, int* out3);
 
 /* Image sessions (PSALM.encode_image / PSALM.segment): the Phi pass split at the end of the prompt-independent prefix, precision "f16x3".
  * psalm_phi_prefix: the layer sequence of psalm_phi_forward on the P prefix rows (embeds (P, hidden), positions 0 .. P-1, key_mask (P) u8 all

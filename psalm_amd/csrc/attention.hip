@@ -734,8 +734,8 @@ __global__ void __launch_bounds__(256) phi_rope_prep_f32_kernel(const float* __r
             ld8(sinT + (pos0 + t) * ROT + c0, sn);
 #pragma unroll
             for (int i = 0; i < 8; ++i) {
-                q[i] = q[i] * cs[i] + (c0 < half ? -qo[i] : qo[i]) * sn[i];
-                k[i] = k[i] * cs[i] + (c0 < half ? -ko[i] : ko[i]) * sn[i];
+                q[i] = psalm_rope_elem(q[i], qo[i], cs[i], sn[i], c0 < half, psalm_rope_fused_dim(i));
+                k[i] = psalm_rope_elem(k[i], ko[i], cs[i], sn[i], c0 < half, psalm_rope_fused_dim(i));
             }
         }
 #pragma unroll
@@ -746,6 +746,34 @@ __global__ void __launch_bounds__(256) phi_rope_prep_f32_kernel(const float* __r
     }
     st8(qd, q);
     st8(kd, k);
+}
+
+// The parts of the pre-pass that depend on key_mask and the shape alone, for a caller whose q / k arrive rotated from the GEMM epilogue
+// (psalm_gemm_x3_split_rope): once per forward pass instead of once per layer.  A block per (32-key tile, sequence): Mk / Tk as above; the block
+// of the last tile also zeroes the padding rows [L, Lp) of Qr / Kr of every head (the epilogue never writes them).
+__global__ void __launch_bounds__(256) phi_attention_tables_kernel(const unsigned char* __restrict__ key_mask, float* __restrict__ Qr,
+                                                                   float* __restrict__ Kr, unsigned char* __restrict__ Mk,
+                                                                   unsigned char* __restrict__ Tk, int L, int Lp, int heads) {
+    constexpr int HD = 64;
+    const int b = blockIdx.y;
+    const int t = blockIdx.x * 32 + (threadIdx.x >> 3), c0 = (threadIdx.x & 7) * 8;     // token, 8-wide head-dim chunk (as phi_rope_prep_f32_kernel)
+    __shared__ int tile_all;
+    const bool valid = t < L && key_mask[(long)b * L + min(t, L - 1)] != 0;
+    if (threadIdx.x == 0) tile_all = 1;
+    __syncthreads();
+    if (c0 == 0) {
+        Mk[(long)b * Lp + t] = valid ? 1 : 0;
+        if (!valid) tile_all = 0;
+    }
+    __syncthreads();
+    if (threadIdx.x == 0) Tk[(long)b * (Lp / 32) + blockIdx.x] = tile_all ? 1 : 0;
+    if (t >= L) {                                        // (only in the last tile's block)
+        const float z[8] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
+        for (int h = 0; h < heads; ++h) {
+            st8(Qr + (((long)b * heads + h) * Lp + t) * HD + c0, z);
+            st8(Kr + (((long)b * heads + h) * Lp + t) * HD + c0, z);
+        }
+    }
 }
 
 // SO = true: the output leaves as split-f16 operand columns (hi at `out` + o_off, lo so_kp f16 further; `out` is then the f16 buffer, ldo its
@@ -998,6 +1026,44 @@ extern "C" int psalm_causal_attention_f32_split(const float* qkv, long ld, int q
                                      B, L, heads, head_dim, rot, stream, split_inv, split_kp, "psalm_causal_attention_f32_split");
 }
 
+// The same in two steps, for a caller whose q / k arrive rotated in the workspace (psalm_gemm_x3_split_rope): the tables and the padding rows
+// once per forward pass, then per layer the attention kernel alone -- same launch, same arguments as causal_attention_f32_impl's second one.
+extern "C" int psalm_phi_attention_tables(const unsigned char* key_mask, void* workspace, int B, int L, int heads, void* stream) {
+    PSALM_CHECK_ARG(key_mask && workspace && (uintptr_t)workspace % 16 == 0 && B >= 0 && L >= 0 && heads >= 1,
+                    "psalm_phi_attention_tables: key mask and a 16-byte aligned workspace");
+    if (B == 0 || L == 0) return 0;
+    const int Lp = (L + 31) / 32 * 32;
+    float* Qr = (float*)workspace;
+    float* Kr = Qr + (long)B * heads * Lp * 64;
+    unsigned char* Mk = (unsigned char*)(Kr + (long)B * heads * Lp * 64);
+    unsigned char* Tk = Mk + (long)B * Lp;
+    hipLaunchKernelGGL(phi_attention_tables_kernel, dim3(Lp / 32, B), dim3(256), 0, (hipStream_t)stream, key_mask, Qr, Kr, Mk, Tk, L, Lp, heads);
+    PSALM_LAUNCH_END("psalm_phi_attention_tables");
+}
+extern "C" int psalm_causal_attention_f32_split_prepared(const float* qkv, long ld, int v_off, void* split_out, long ld_split, int split_kp,
+                                                         int split_col_off, const float* split_inv, void* workspace, int B, int L, int heads,
+                                                         int head_dim, void* stream) {
+    PSALM_CHECK_ARG(head_dim == 64, "psalm_causal_attention_f32_split_prepared: head_dim 64 (Phi-1.5)");
+    PSALM_CHECK_ARG(split_out && split_inv && ld_split >= 2L * split_kp && split_col_off + heads * 64 <= split_kp,
+                    "psalm_causal_attention_f32_split_prepared: split buffer rows of >= 2*split_kp f16 and the row scales");
+    PSALM_CHECK_ARG(ld % 4 == 0 && v_off % 4 == 0 && (uintptr_t)qkv % 16 == 0 && (uintptr_t)split_out % 16 == 0 && workspace &&
+                        (uintptr_t)workspace % 16 == 0 && ld_split % 8 == 0 && split_col_off % 8 == 0 && split_kp % 8 == 0,
+                    "psalm_causal_attention_f32_split_prepared: 16-byte aligned rows / offsets and a workspace");
+    if (B == 0 || L == 0) return 0;
+    PSALM_CHECK_ARG(((long)L - 1) * ld * 4 + 256 < 0x7fffffffL, "psalm_causal_attention_f32_split_prepared: L * ld * 4 must stay below 2 GiB (buffer-descriptor fetches)");
+    const int Lp = (L + 31) / 32 * 32;
+    const float* Qr = (const float*)workspace;
+    const float* Kr = Qr + (long)B * heads * Lp * 64;
+    const unsigned char* Mk = (const unsigned char*)(Kr + (long)B * heads * Lp * 64);
+    const unsigned char* Tk = Mk + (long)B * Lp;
+    const int pair = 1, nqt = Lp / 32;                                    // (as causal_attention_f32_impl)
+    const dim3 grid(pair ? (nqt + 1) / 2 : nqt, heads, B);
+    const int xcd_heads = ((heads * B) % 8 == 0 && psalm_get_tuning(PSALM_TUNE_ATTN_XCD_HEADS)) ? 1 : 0;
+    hipLaunchKernelGGL(causal_attention_f32_splitk_kernel<true>, grid, dim3(256), 0, (hipStream_t)stream, Qr, Kr, Mk, Tk, qkv, ld, v_off,
+                       (float*)split_out, ld_split, split_col_off, L, Lp, heads, split_inv, split_kp, pair, xcd_heads);
+    PSALM_LAUNCH_END("psalm_causal_attention_f32_split_prepared");
+}
+
 // ---- prefix form (image sessions: one image, many prompts).  The sequence of every prompt is [prefix of P rows | suffix of S rows]; the prefix --
 // system text + image tokens -- is the same for all N prompts, so its RoPE'd K and its V were computed ONCE per layer (psalm_phi_prefix_kv_store)
 // and only the N * S suffix rows carry queries.  Suffix query s of prompt n sees the P prefix keys (all real) and the suffix keys s' <= s of its
@@ -1028,7 +1094,7 @@ __global__ void __launch_bounds__(256) phi_prefix_kv_store_kernel(const float* _
             ld8(cosT + (long)t * ROT + c0, cs);
             ld8(sinT + (long)t * ROT + c0, sn);
 #pragma unroll
-            for (int i = 0; i < 8; ++i) k[i] = k[i] * cs[i] + (c0 < half ? -ko[i] : ko[i]) * sn[i];
+            for (int i = 0; i < 8; ++i) k[i] = psalm_rope_elem(k[i], ko[i], cs[i], sn[i], c0 < half, psalm_rope_fused_dim(i));
         }
         float v[8];
         ld8(p + v_off + h * HD + c0, v);

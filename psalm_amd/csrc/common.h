@@ -139,6 +139,7 @@ __device__ __forceinline__ void psalm_split_words(float y, unsigned& hw, unsigne
 #ifdef PSALM_EMU_BUILD
 __device__ __forceinline__ unsigned psalm_swap_adjacent(unsigned v) { return __shfl_xor(v, 1); }   // value of lane ^ 1
 __device__ __forceinline__ unsigned psalm_quad_swap2(unsigned v) { return __shfl_xor(v, 2); }      // value of lane ^ 2
+__device__ __forceinline__ unsigned psalm_swap_row16(unsigned v) { return __shfl_xor(v, 16); }     // value of lane ^ 16
 template <int P> __device__ __forceinline__ unsigned psalm_quad_bcast(unsigned v) { return __shfl(v, ((threadIdx.x & 63) & ~3) | P); }   // lane P of this lane's group of 4
 struct psalm_rsrc { char* base; unsigned bytes; };
 __device__ __forceinline__ psalm_rsrc psalm_make_rsrc(const void* p, unsigned bytes) { return psalm_rsrc{(char*)p, bytes}; }
@@ -160,6 +161,9 @@ __device__ __forceinline__ unsigned psalm_swap_adjacent(unsigned v) {           
 __device__ __forceinline__ unsigned psalm_quad_swap2(unsigned v) {                                 // DPP quad_perm [2,3,0,1]
     return (unsigned)__builtin_amdgcn_mov_dpp((int)v, 0x4E, 0xF, 0xF, true);
 }
+// value of lane ^ 16 (the other 16-lane row of this lane's group of 32): ds_swizzle in bit mode (and 0x1f, or 0, xor 0x10) -- the LDS crossbar
+// without an address register or LDS memory; DPP on gfx950 has no cross-row xor
+__device__ __forceinline__ unsigned psalm_swap_row16(unsigned v) { return (unsigned)__builtin_amdgcn_ds_swizzle((int)v, 0x401F); }
 template <int P> __device__ __forceinline__ unsigned psalm_quad_bcast(unsigned v) {                // DPP quad_perm [P,P,P,P]: lane P of the group of 4
     return (unsigned)__builtin_amdgcn_mov_dpp((int)v, P * 0x55, 0xF, 0xF, true);
 }
@@ -193,6 +197,21 @@ __device__ __forceinline__ psalm_u32x4 psalm_buf_load_b128_s(psalm_rsrc r, unsig
 }
 #endif
 
+// ---- Phi RoPE (rotate_half over the first 32 of the 64 head dimensions) of ONE element: x at rotary dimension c, xo its partner (dimension
+// c + 16 for c < 16 -- `neg`, the partner enters negated -- else c - 16), cs / sn the cos / sin table entries of (position, c).  One function
+// for every kernel that rotates (the pre-pass phi_rope_prep_f32_kernel, phi_prefix_kv_store_kernel, the [k|v|q|fc1] GEMM's epilogue): their
+// outputs are compared bit for bit.  The arithmetic is spelled out, contraction off, in the form the pre-pass's `x * cs + (+-xo) * sn` over an
+// 8-element chunk had always been compiled to: the partner product is rounded; elements 0..5 of the chunk (c % 8 < 6) then take ONE fma, elements
+// 6 and 7 a rounded x * cs and an add (the vectoriser had paired six elements into v_pk_fma_f32 and left the last pair as v_pk_mul + v_pk_add).
+__device__ __forceinline__ float psalm_rope_elem(float x, float xo, float cs, float sn, bool neg, bool fused) {
+#pragma clang fp contract(off)
+    const float t = (neg ? -xo : xo) * sn;
+    const float p = x * cs;
+    return fused ? fmaf(x, cs, t) : p + t;
+}
+// (c % 8 < 6: see above)
+__device__ __forceinline__ bool psalm_rope_fused_dim(int c) { return (c & 7) < 6; }
+
 // ----------------------------------------------------------------------------- host side
 extern "C" void psalm_set_error(const char* msg);
 extern "C" int psalm_get_tuning(int key);          // api.hip; keys: PSALM_TUNE_* (mirrored from include/psalm_hip.h for the translation units that do not include it)
@@ -203,6 +222,7 @@ extern "C" int psalm_get_tuning(int key);          // api.hip; keys: PSALM_TUNE_
 #define PSALM_TUNE_DECODER_FUSE 3
 #define PSALM_TUNE_ROW_GROUPS 4
 #define PSALM_TUNE_MHA_QTILE_WAVES 5
+#define PSALM_TUNE_PHI_ROPE_EPILOGUE 6
 #define PSALM_TUNE_COUNT 8
 #endif
 

@@ -23,6 +23,7 @@
 // blockIdx -> tile mapping is XCD-aware: consecutive tiles along N (sharing the A row-panel) are placed on the
 // same XCD (block b runs on XCD b % 8) so the panel is fetched into that XCD's L2 once.
 #include "common.h"
+#include "psalm_hip.h"      // psalm_rope_out
 #include <algorithm>
 #include <atomic>
 #include <cstring>
@@ -340,6 +341,15 @@ struct GemmFastArgs {
     // A rows per XCD, 8 x 38 MB of operand reads from the fabric for 129 MB of compulsory traffic (profiles/r05_pmc_hbm_traffic.json: 3.6x).
     // With slice = linear id % splits the blocks of one XCD share a K slice: each A / W slice is fetched into one XCD's L2 (two when splits = 4 ...).
     int xcd_ksplit = 0;
+    // RoPE hand-over of the paired split-output forms (psalm_gemm_x3_split_rope; rope_qr == nullptr: off).  The 64 columns of a wavefront that lie in
+    // [rope_k_col, + 64 heads) / [rope_q_col, ...) are one head's k / q: they leave rotated (q also scaled) for the Phi attention kernel --
+    // element (row b L + t, head h, dim d) at ((b heads + h) Lp + t) 64 + d of rope_kr / rope_qr -- instead of going to C.
+    float* rope_qr = nullptr;
+    float* rope_kr = nullptr;
+    const float* rope_cos = nullptr;
+    const float* rope_sin = nullptr;
+    int rope_q_col = 0, rope_k_col = 0, rope_heads = 0, rope_B = 0, rope_L = 0, rope_Lp = 0;
+    float rope_scale = 0.f;
 };
 // scale / inverse scale of a split-f16 row from an upper bound of its magnitudes: bound * sc in [2^12, 2^13)
 __device__ __forceinline__ void split_scale_from_bound(float bound, float& sc, float& inv) {
@@ -989,6 +999,65 @@ __global__ void __launch_bounds__(64 * (WM * WN + (PH8_ == 6 ? 2 : (PH8_ == 7 ? 
         bool lds_path = !split && ((act != ACT_NONE && act != ACT_RELU && bn + BN > g.act_col_start) || (g.act & ACT_BIAS_ROW) != 0);
         if constexpr (SO) lds_path = lds_path || (fa.so != nullptr && bn + BN > fa.so_col_start);
         if (!lds_path) {
+            // ---- RoPE hand-over (GemmFastArgs::rope_qr; the paired split-output instantiations): a wavefront whose 64 columns are one head's k or q
+            // rotates them here, where every element sits in a register, and stores them head-major for the attention kernel -- what the
+            // attention's pre-pass did by re-reading C (15 MB written + 15 MB read per Phi layer for the hand-over alone).  Lane n32 of column tile
+            // j owns head dimension 32 j + n32: the rotary dimensions 0..31 are tile 0, the partner of dimension c < 16 is c + 16 = lane n32 ^ 16 of
+            // the same tile (one ds_swizzle per element).  Row b L + t goes to sequence b, position t: the 32 rows of an m-tile start at a
+            // wave-uniform (b, t) and cross at most one sequence boundary (host: L >= 32 when B > 1).  Rows >= M are dropped by the descriptor.
+            if constexpr (SO && PAIR) {
+                if (fa.rope_qr != nullptr) {
+                    static_assert(BN / WN == 64 && TN == 2 && X3 != 0, "RoPE epilogue: a wavefront's columns are one 64-wide head");
+                    const int wc0 = bn + wn * (BN / WN), nrot = fa.rope_heads * 64;
+                    const bool is_q = wc0 >= fa.rope_q_col && wc0 < fa.rope_q_col + nrot;
+                    const bool is_k = wc0 >= fa.rope_k_col && wc0 < fa.rope_k_col + nrot;
+                    if (is_q || is_k) {
+                        const int L = fa.rope_L, Lp = fa.rope_Lp;
+                        const int head = (wc0 - (is_q ? fa.rope_q_col : fa.rope_k_col)) >> 6;
+                        const psalm_rsrc rd = psalm_make_rsrc(is_q ? fa.rope_qr : fa.rope_kr, (unsigned)((long)fa.rope_B * fa.rope_heads * Lp * 256));
+                        const psalm_rsrc rcs = psalm_make_rsrc(fa.rope_cos, (unsigned)L * 128u), rsn = psalm_make_rsrc(fa.rope_sin, (unsigned)L * 128u);
+                        const unsigned hoff = (unsigned)head * (unsigned)Lp * 256u;                   // wave-uniform: this head's plane
+                        const unsigned next_seq = (unsigned)(fa.rope_heads * Lp - L) * 256u;         // from (b, L + t') to (b + 1, t')
+                        const float qs = is_q ? fa.rope_scale : 1.f;                                  // (x * 1 is x)
+                        const bool neg = n32 < 16, fused = psalm_rope_fused_dim(n32);
+                        const int c0 = wc0 + n32;
+                        const float wsc0 = fa.w_scale[c0], wsc1 = fa.w_scale[c0 + 32];
+                        const float bias0 = g.bias ? g.bias[c0] : 0.f, bias1 = g.bias ? g.bias[c0 + 32] : 0.f;
+#pragma unroll
+                        for (int i = 0; i < TM; ++i) {
+                            const int rbase = bm + wm * (BM / WM) + i * 32;                           // wave-uniform
+                            const int sb = rbase / L, t0 = rbase - sb * L;
+                            const unsigned seq0 = ((unsigned)(sb * fa.rope_heads) * (unsigned)Lp + (unsigned)t0) * 256u;
+                            float asc[16], cs[16], sn[16];
+                            unsigned off[16];
+#pragma unroll
+                            for (int r = 0; r < 16; ++r) {
+                                const int rr = 4 * hi + (r & 3) + 8 * (r >> 2), row = rbase + rr;
+                                const bool ok = row < g.M, wrap = t0 + rr >= L;
+                                const int t = wrap ? t0 + rr - L : t0 + rr;
+                                asc[r] = fa.a_scale[min(row, g.M - 1)];
+                                const unsigned toff = ok ? (unsigned)t * 128u + (unsigned)n32 * 4u : PSALM_BUF_OOB;
+                                cs[r] = psalm_buf_load_f32(rcs, toff);
+                                sn[r] = psalm_buf_load_f32(rsn, toff);
+                                off[r] = ok ? seq0 + (unsigned)rr * 256u + (wrap ? next_seq : 0u) + (unsigned)n32 * 4u : PSALM_BUF_OOB;
+                            }
+#pragma unroll
+                            for (int r = 0; r < 16; ++r) {
+                                // (+ 0: the fp32 path below adds the absent residual's zero before the value reaches C, which turns -0 into +0)
+                                const float x0 = fmaf(acc[i][0][r], asc[r] * wsc0, bias0) + 0.f, x1 = fmaf(acc[i][1][r], asc[r] * wsc1, bias1) + 0.f;
+                                const float xo = __builtin_bit_cast(float, psalm_swap_row16(__builtin_bit_cast(unsigned, x0)));
+                                const float y0 = psalm_rope_elem(x0, xo, cs[r], sn[r], neg, fused) * qs, y1 = x1 * qs;
+                                psalm_buf_store_f32_s(y0, rd, off[r], hoff);
+                                psalm_buf_store_f32_s(y1, rd, off[r] == PSALM_BUF_OOB ? off[r] : off[r] + 128u, hoff);
+                            }
+                        }
+                        PSALM_TL(4);
+                        PSALM_TL_DRAIN();
+                        PSALM_TL(5);
+                        return;
+                    }
+                }
+            }
             const bool post = (g.act & ACT_POST_RESIDUAL) != 0;
             float* Cb = split ? fa.slab + (long)ksl * g.M * g.N : (float*)g.C;
             const long ldo = split ? (long)g.N : g.ldc;
@@ -2603,7 +2672,8 @@ extern "C" int psalm_split_f16(const float* x, long ldx, void* out, long ldo, fl
 // C = act((A . W^T) + bias) + residual from split-f16 operands:  A2 (M, 2 Kp) / W2 (N, 2 Kp) f16 [hi | lo] with row strides lda / ldw
 // (elements) and per-row scales a_scale (M) / w_scale (N) as written by psalm_split_f16;  Kp % 64 == 0.  C / residual fp32.
 // Same tile selection, split-K and epilogue as psalm_gemm (on a K range of 3 Kp); M <= 128 problems take the skinny kernel.
-struct SplitOut { void* so; long ldso; int so_kp, so_col_off, so_col_start, so_global; float* so_inv; const float* so_par; int so_paired; };
+struct SplitOut { void* so; long ldso; int so_kp, so_col_off, so_col_start, so_global; float* so_inv; const float* so_par; int so_paired;
+                  const psalm_rope_out* rope = nullptr; };
 static int gemm_x3_impl(const void* A2, long lda, const float* a_scale, const void* W2, long ldw, const float* w_scale, int Kp,
                         const float* bias, const void* residual, long ldr, void* C, long ldc, int M, int N, int act,
                         int act_col_start, void* workspace, long workspace_bytes, void* stream, const SplitOut* so, const char* name,
@@ -2635,6 +2705,12 @@ static int gemm_x3_impl(const void* A2, long lda, const float* a_scale, const vo
         fa.so = (unsigned short*)so->so; fa.ldso = so->ldso; fa.so_kp = so->so_kp; fa.so_col_off = so->so_col_off;
         fa.so_col_start = so->so_col_start; fa.so_global = so->so_global; fa.so_inv = so->so_inv; fa.so_par = so->so_par;
         fa.so_paired = so->so_paired;
+        if (so->rope) {
+            const psalm_rope_out* ro = so->rope;
+            fa.rope_qr = ro->Qr; fa.rope_kr = ro->Kr; fa.rope_cos = ro->cos_table; fa.rope_sin = ro->sin_table;
+            fa.rope_q_col = ro->q_col; fa.rope_k_col = ro->k_col; fa.rope_heads = ro->heads; fa.rope_B = ro->B; fa.rope_L = ro->L; fa.rope_Lp = ro->Lp;
+            fa.rope_scale = ro->scale;
+        }
     }
     return launch_fast(g, fa, false, PSALM_F32, workspace, workspace_bytes, s, ln, true, select_m);
 }
@@ -2677,6 +2753,43 @@ extern "C" int psalm_gemm_x3_split(const void* A2, long lda, const float* a_scal
     SplitOut so{split_out, ld_split, split_kp, split_col_off, split_col_start, global_rows, split_inv, bound_par, paired};
     return gemm_x3_impl(A2, lda, a_scale, W2, ldw, w_scale, Kp, bias, nullptr, 0, C, ldc, M, N, act, act_col_start, workspace, workspace_bytes,
                         stream, &so, "psalm_gemm_x3_split");
+}
+// ... whose k and q columns leave rotated / scaled in the attention kernel's head-major layout instead of going to C (GemmFastArgs::rope_qr; the
+// epilogue of every PAIRED split-output instantiation, i.e. of every kernel a paired call can select).  What the element code assumes is checked
+// here: whole 64-column heads below split_col_start and outside the activated columns, rows that are B sequences of L, at most one sequence
+// boundary per 32-row matrix tile, destinations within a buffer descriptor.
+extern "C" int psalm_gemm_x3_split_rope(const void* A2, long lda, const float* a_scale, const void* W2, long ldw, const float* w_scale, int Kp,
+                                        const float* bias, void* C, long ldc, int M, int N, int act, int act_col_start, void* split_out,
+                                        long ld_split, int split_kp, int split_col_off, int split_col_start, int paired, float* split_inv,
+                                        const float* bound_par, int global_rows, const psalm_rope_out* rope, void* workspace,
+                                        long workspace_bytes, void* stream) {
+    PSALM_CHECK_ARG(rope && rope->Qr && rope->Kr && rope->cos_table && rope->sin_table, "psalm_gemm_x3_split_rope: Qr, Kr and the cos / sin tables required");
+    PSALM_CHECK_ARG(paired == 1, "psalm_gemm_x3_split_rope: the RoPE epilogue belongs to the paired split-output forms");
+    const long nrot = 64L * rope->heads;
+    PSALM_CHECK_ARG(rope->heads >= 1 && rope->q_col >= 0 && rope->k_col >= 0 && rope->q_col % 64 == 0 && rope->k_col % 64 == 0 &&
+                        rope->q_col + nrot <= split_col_start && rope->k_col + nrot <= split_col_start &&
+                        (rope->q_col + nrot <= rope->k_col || rope->k_col + nrot <= rope->q_col),
+                    "psalm_gemm_x3_split_rope: q / k are heads * 64 columns each, at multiples of 64 below split_col_start, disjoint");
+    // (a tile that holds activated columns takes the LDS epilogue as a whole: none of them may hold q / k columns -- tiles are 128 or 256 wide)
+    PSALM_CHECK_ARG((act & ~15) == 0 && ((act & 15) == 0 || (act_col_start % 256 == 0 && rope->q_col + nrot <= act_col_start &&
+                                                               rope->k_col + nrot <= act_col_start)),
+                    "psalm_gemm_x3_split_rope: q / k columns carry no activation, act_col_start % 256 == 0, no activation flags");
+    PSALM_CHECK_ARG(rope->B >= 1 && rope->L >= 1 && (long)rope->B * rope->L == M && rope->Lp == (rope->L + 31) / 32 * 32 &&
+                        (rope->B == 1 || rope->L >= 32),
+                    "psalm_gemm_x3_split_rope: M == B * L rows, Lp == ceil32(L), L >= 32 when B > 1");
+    PSALM_CHECK_ARG((long)rope->B * rope->heads * rope->Lp * 256 < 0x7ffff000L && (long)rope->L * 128 < 0x7ffff000L,
+                    "psalm_gemm_x3_split_rope: Qr / Kr must stay below 2 GiB each (buffer-descriptor stores)");
+    PSALM_CHECK_ARG(split_col_start % 256 == 0 && (N - split_col_start) % 64 == 0 && (long)M * ld_split * 2 < (1L << 31),
+                    "psalm_gemm_x3_split: paired output needs split_col_start % 256 == 0, (N - split_col_start) % 64 == 0, split_out < 2 GiB");
+    PSALM_CHECK_ARG(split_out && split_inv && bound_par, "psalm_gemm_x3_split: split output, scale array and bound parameters required");
+    PSALM_CHECK_ARG(N % 8 == 0 && split_col_start % 8 == 0 && split_col_start >= 0 && split_col_start < N && split_col_off % 8 == 0 &&
+                        split_col_off >= 0 && split_kp % 8 == 0 && (uintptr_t)split_out % 16 == 0 && (ld_split * 2) % 16 == 0 &&
+                        split_col_off + (N - split_col_start) <= split_kp && ld_split >= 2L * split_kp,
+                    "psalm_gemm_x3_split: N / column offsets multiples of 8, 16-byte aligned split rows of >= 2*split_kp f16");
+    PSALM_CHECK_ARG(C || split_col_start == 0, "psalm_gemm_x3_split: C required for the columns below split_col_start");
+    SplitOut so{split_out, ld_split, split_kp, split_col_off, split_col_start, global_rows, split_inv, bound_par, paired, rope};
+    return gemm_x3_impl(A2, lda, a_scale, W2, ldw, w_scale, Kp, bias, nullptr, 0, C, ldc, M, N, act, act_col_start, workspace, workspace_bytes,
+                        stream, &so, "psalm_gemm_x3_split_rope");
 }
 
 

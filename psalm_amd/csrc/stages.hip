@@ -46,6 +46,28 @@ extern "C" long psalm_phi_forward_workspace(const psalm_phi_desc* d, int B, int 
     return phi_layout(d, B, L).total;
 }
 
+// Does psalm_phi_forward rotate q / k in the [k|v|q|fc1] GEMM's epilogue (PSALM_TUNE_PHI_ROPE_EPILOGUE)?  Host-side, from the descriptor and the
+// shape alone: every layer's fc1 rows in the paired layout (every kernel a paired call selects carries the epilogue; a tile policy without a
+// paired form is an error of the GEMM with and without it), k / q in whole 256-column tiles, and what psalm_gemm_x3_split_rope asks of the shape.
+static bool phi_rope_epilogue(const psalm_phi_desc* d, int B, int L) {
+    const long Lp = (L + 31) / 32 * 32;
+    bool ok = psalm_get_tuning(PSALM_TUNE_PHI_ROPE_EPILOGUE) != 0 && d->head_dim == 64 && d->rot == 32 && (3 * d->hidden) % 256 == 0 &&
+              (B == 1 || L >= 32) && (long)B * d->heads * Lp * 256 < 0x7ffff000L && (long)L * 128 < 0x7ffff000L;
+    for (int i = 0; i < d->num_layers && ok; ++i) ok = d->layers[i].paired == 1;
+    return ok;
+}
+// The launch sequence psalm_phi_forward issues for (d, B, L) under the current switches: out3 = {1 when q / k are rotated in the GEMM epilogue,
+// launches per layer, launches in front of the layer loop}.
+extern "C" int psalm_phi_forward_plan(const psalm_phi_desc* d, int B, int L, int* out3) {
+    if (phi_check(d) != 0) return -1;
+    PSALM_CHECK_ARG(out3 && B > 0 && L > 0, "psalm_phi_forward_plan: null argument");
+    const bool ep = phi_rope_epilogue(d, B, L);
+    out3[0] = ep ? 1 : 0;
+    out3[1] = ep ? 4 : 5;                  // [k|v|q|fc1] (+ RoPE pre-pass) + attention + [dense|fc2] slices + reduce / LayerNorm
+    out3[2] = ep ? 2 : 1;                  // layer 0's LayerNorm (+ the attention tables)
+    return 0;
+}
+
 extern "C" int psalm_phi_forward(const psalm_phi_desc* d, const float* embeds, const unsigned char* key_mask, const float* cos_table,
                                  const float* sin_table, int B, int L, float* hidden_out, void* workspace, long workspace_bytes,
                                  void* gemm_workspace, long gemm_workspace_bytes, void* stream) {
@@ -69,20 +91,41 @@ extern "C" int psalm_phi_forward(const psalm_phi_desc* d, const float* embeds, c
     // layer 0's input LayerNorm, straight into split form (model.py: o.layernorm_split(x, llm0.ln))
     rc = psalm_layernorm_split(embeds, H, nullptr, H, l0->ln_g, l0->ln_b, M, H, d->ln_eps, h, hinv, nullptr, 0, nullptr, nullptr, stream);
     if (rc) return rc;
+    // RoPE in the [k|v|q|fc1] GEMM's epilogue (PSALM_TUNE_PHI_ROPE_EPILOGUE): q / k reach the attention workspace rotated, straight from the
+    // accumulators, and the key-mask tables are built once -- four launches per layer instead of five.  Decided here on the host, once for
+    // the whole pass and before the first launch that differs (phi_rope_epilogue); otherwise the pre-pass sequence.
+    const int Lp = (L + 31) / 32 * 32;
+    const bool rope_ep = phi_rope_epilogue(d, B, L);
+    const float* Qr = (const float*)attn;
+    const psalm_rope_out rope{(float*)Qr, (float*)Qr + (long)B * d->heads * Lp * 64, cos_table, sin_table, 2 * H, 0, d->heads, B, L, Lp,
+                              1.0f / sqrtf((float)d->head_dim), 0};
+    if (rope_ep) {
+        rc = psalm_phi_attention_tables(key_mask, attn, B, L, d->heads, stream);
+        if (rc) return rc;
+    }
     const float* xin = embeds;
     int cur = 0;
     for (int i = 0; i < d->num_layers; ++i) {
         const psalm_phi_layer* ly = &d->layers[i];
         const bool last = i == d->num_layers - 1;
         PSALM_CHECK_ARG(ly->w1 && ly->w1_scale && ly->b1 && ly->w2 && ly->w2_scale && ly->b2 && ly->bnd, "psalm_phi_forward: layer weights missing");
-        // [k | v | q | gelu_new(fc1)]: k, v, q -> big (fp32), gelu(fc1) -> columns [H, H + I) of the operand a2 with the row scales inv2
-        rc = psalm_gemm_x3_split(h, 2L * Kp, hinv, ly->w1, 2L * Kp, ly->w1_scale, Kp, ly->b1, big, 3L * H, M, 3 * H + I, /*gelu_new*/ 3, 3 * H, a2,
-                                 2L * K2, K2, H, 3 * H, ly->paired, inv2, ly->bnd, 1, gemm_workspace, gemm_workspace_bytes, stream);
-        if (rc) return rc;
-        // RoPE + causal attention (q at 2H, k at 0, v at H of big) -> columns [0, H) of a2 under the same row scales
-        rc = psalm_causal_attention_f32_split(big, 3L * H, 2 * H, 0, H, a2, 2L * K2, K2, 0, inv2, cos_table, sin_table, key_mask, attn, B, L, d->heads,
-                                              d->head_dim, d->rot, stream);
-        if (rc) return rc;
+        if (rope_ep) {
+            // [k | v | q | gelu_new(fc1)]: v -> big (fp32), RoPE(k) / scaled RoPE(q) -> the attention workspace, gelu(fc1) -> a2 as below
+            rc = psalm_gemm_x3_split_rope(h, 2L * Kp, hinv, ly->w1, 2L * Kp, ly->w1_scale, Kp, ly->b1, big, 3L * H, M, 3 * H + I, /*gelu_new*/ 3, 3 * H,
+                                          a2, 2L * K2, K2, H, 3 * H, ly->paired, inv2, ly->bnd, 1, &rope, gemm_workspace, gemm_workspace_bytes, stream);
+            if (rc) return rc;
+            rc = psalm_causal_attention_f32_split_prepared(big, 3L * H, H, a2, 2L * K2, K2, 0, inv2, attn, B, L, d->heads, d->head_dim, stream);
+            if (rc) return rc;
+        } else {
+            // [k | v | q | gelu_new(fc1)]: k, v, q -> big (fp32), gelu(fc1) -> columns [H, H + I) of the operand a2 with the row scales inv2
+            rc = psalm_gemm_x3_split(h, 2L * Kp, hinv, ly->w1, 2L * Kp, ly->w1_scale, Kp, ly->b1, big, 3L * H, M, 3 * H + I, /*gelu_new*/ 3, 3 * H, a2,
+                                     2L * K2, K2, H, 3 * H, ly->paired, inv2, ly->bnd, 1, gemm_workspace, gemm_workspace_bytes, stream);
+            if (rc) return rc;
+            // RoPE + causal attention (q at 2H, k at 0, v at H of big) -> columns [0, H) of a2 under the same row scales
+            rc = psalm_causal_attention_f32_split(big, 3L * H, 2 * H, 0, H, a2, 2L * K2, K2, 0, inv2, cos_table, sin_table, key_mask, attn, B, L, d->heads,
+                                                  d->head_dim, d->rot, stream);
+            if (rc) return rc;
+        }
         float* xout = x[cur];
         if (last || H % 64 != 0 || H > 2048) {
             rc = psalm_gemm_x3(a2, 2L * K2, inv2, ly->w2, 2L * K2, ly->w2_scale, K2, ly->b2, xin, H, xout, H, M, H, 0, 0, gemm_workspace,

@@ -49,7 +49,7 @@ def _dt(t: torch.Tensor) -> int:
         raise PsalmHipError(f"unsupported dtype {t.dtype} (float32 / bfloat16 only)")
 
 
-ABI_VERSION = 15       # == PSALM_ABI_VERSION of include/psalm_hip.h (tests/test_0_abi.py compares the two and the built library's answer)
+ABI_VERSION = 16       # == PSALM_ABI_VERSION of include/psalm_hip.h (tests/test_0_abi.py compares the two and the built library's answer)
 
 
 class _ProfiledLib:
@@ -131,6 +131,11 @@ class _PostIO(ctypes.Structure):             # psalm_post_io
 class _PhiLayer(ctypes.Structure):           # psalm_phi_layer of include/psalm_hip.h
     _fields_ = [("w1", c_void_p), ("w1_scale", c_void_p), ("b1", c_void_p), ("w2", c_void_p), ("w2_scale", c_void_p), ("b2", c_void_p),
                 ("ln_g", c_void_p), ("ln_b", c_void_p), ("bnd", c_void_p), ("paired", c_int)]
+
+
+class _RopeOut(ctypes.Structure):            # psalm_rope_out
+    _fields_ = [("Qr", c_void_p), ("Kr", c_void_p), ("cos_table", c_void_p), ("sin_table", c_void_p), ("q_col", c_int), ("k_col", c_int),
+                ("heads", c_int), ("B", c_int), ("L", c_int), ("Lp", c_int), ("scale", c_float), ("pad_", c_int)]
 
 
 class _PhiDesc(ctypes.Structure):            # psalm_phi_desc
@@ -381,11 +386,13 @@ class Ops:
         return x, SplitF16(so, inv, N), y
 
     def gemm_x3_split(self, a, w, bias, act, split_out, split_inv, bound_par, split_col_off=0, split_col_start=0, act_col_start=0,
-                      out=None, global_rows=False, paired=False):
+                      out=None, global_rows=False, paired=False, rope=None):
         """gemm_x3 whose columns >= split_col_start are written as the split-f16 A operand of the next GEMM: into `split_out` (a SplitF16's
         .t buffer (M, 2*Kp_out) f16) at columns split_col_off.. (hi) / Kp_out + split_col_off.. (lo), row scales (inverse) into split_inv;
         bound_par: 4 device floats, see psalm_gemm_x3_split.  Columns below split_col_start go to `out` (M, >= split_col_start...) fp32.
-        paired: the rows of `w` (and bias) >= split_col_start were permuted with `so_pair_perm` (stores straight from the accumulators)."""
+        paired: the rows of `w` (and bias) >= split_col_start were permuted with `so_pair_perm` (stores straight from the accumulators).
+        rope: dict(ws=, cos=, sin=, q_col=, k_col=, heads=, B=, L=) -- psalm_gemm_x3_split_rope: the k / q columns leave rotated (q scaled) in
+        the attention workspace `ws` (causal_attention_workspace) instead of going to `out`."""
         a, w = self._x3_operands(a, w)
         M, N = a.t.shape[0], w.t.shape[0]
         if split_out.dtype != torch.float16 or split_out.dim() != 2 or split_out.shape[0] != M or split_out.stride(1) != 1:
@@ -396,13 +403,24 @@ class Ops:
             raise PsalmHipError("gemm_x3_split: float32 `out` required for the columns below split_col_start")
         if bias is not None and (bias.dtype != torch.float32 or bias.numel() != N):
             raise PsalmHipError("gemm bias must be float32 (N,)")
-        rc = self.lib.psalm_gemm_x3_split(self._p(a.t), c_long(a.t.stride(0)), self._p(a.inv_scale), self._p(w.t), c_long(w.t.stride(0)),
-                                          self._p(w.inv_scale), a.Kp, self._pv(bias), self._pv(out),
-                                          c_long(out.stride(0) if out is not None else 0), M, N, act, act_col_start,
-                                          self._p(split_out), c_long(split_out.stride(0)), split_out.shape[1] // 2, split_col_off,
-                                          split_col_start, int(bool(paired)), self._p(split_inv), self._p(bound_par), int(bool(global_rows)),
-                                          self._p(self._gemm_ws()), c_long(self.GEMM_WS_BYTES), self._stream())
-        self._check(rc, "psalm_gemm_x3_split")
+        head = (self._p(a.t), c_long(a.t.stride(0)), self._p(a.inv_scale), self._p(w.t), c_long(w.t.stride(0)), self._p(w.inv_scale), a.Kp,
+                self._pv(bias), self._pv(out), c_long(out.stride(0) if out is not None else 0), M, N, act, act_col_start, self._p(split_out),
+                c_long(split_out.stride(0)), split_out.shape[1] // 2, split_col_off, split_col_start, int(bool(paired)), self._p(split_inv),
+                self._p(bound_par), int(bool(global_rows)))
+        tail = (self._p(self._gemm_ws()), c_long(self.GEMM_WS_BYTES), self._stream())
+        if rope is not None:
+            B, L, heads = rope["B"], rope["L"], rope["heads"]
+            Lp = (L + 31) // 32 * 32
+            ws = rope["ws"]
+            if ws.dtype != torch.uint8 or ws.numel() < self.causal_attention_workspace_bytes(B, L, heads) or ws.data_ptr() % 16:
+                raise PsalmHipError("gemm_x3_split: rope['ws'] is a causal_attention_workspace(B, L, heads)")
+            ro = _RopeOut(ws.data_ptr(), ws.data_ptr() + B * heads * Lp * 64 * 4, rope["cos"].data_ptr(), rope["sin"].data_ptr(), rope["q_col"],
+                          rope["k_col"], heads, B, L, Lp, 1.0 / math.sqrt(64.0), 0)
+            rc = self.lib.psalm_gemm_x3_split_rope(*head, ctypes.byref(ro), *tail)
+            self._check(rc, "psalm_gemm_x3_split_rope")
+        else:
+            rc = self.lib.psalm_gemm_x3_split(*head, *tail)
+            self._check(rc, "psalm_gemm_x3_split")
         if _DEBUG_BOUNDS or self.debug_bounds:
             self.check_split_bound(split_out, split_col_off, N - split_col_start, "gemm_x3_split")
         return split_out
@@ -831,9 +849,16 @@ class Ops:
     def _pi(t):
         return None if t is None else t.data_ptr()
 
+    def phi_forward_plan(self, desc, B, L):
+        """psalm_phi_forward_plan: (q / k rotated in the GEMM epilogue, launches per layer, launches in front of the layer loop) of phi_forward"""
+        out = (c_int * 3)()
+        self._check(self._cdll_raw.psalm_phi_forward_plan(ctypes.byref(desc), B, L, out), "psalm_phi_forward_plan")
+        return bool(out[0]), out[1], out[2]
+
     def phi_forward(self, desc, embeds, key_mask, cos, sin, B, L):
         """PhiModel.forward over inputs_embeds (B*L, hidden) float32 as ONE native call (psalm_phi_forward): returns the final-LayerNorm hidden
-        states (B*L, hidden) float32.  Same launches, same order, same bits as PSALM.llm's op-by-op sequence."""
+        states (B*L, hidden) float32.  Same bits as PSALM.llm's op-by-op sequence, which keeps the RoPE pre-pass per layer; the native call
+        rotates q / k in the [k|v|q|fc1] GEMM's epilogue where `phi_forward_plan` says so (TUNE_PHI_ROPE_EPILOGUE)."""
         if embeds.dtype != torch.float32 or embeds.dim() != 2 or embeds.shape[0] != B * L or embeds.shape[1] != desc.hidden:
             raise PsalmHipError("phi_forward: float32 (B*L, hidden) embeddings")
         self.lib.psalm_phi_forward_workspace.restype = c_long
@@ -938,6 +963,7 @@ class Ops:
         self._check(self.lib.psalm_gemm_x3_set_products(int(n)), "psalm_gemm_x3_set_products")
 
     TUNE_GEMM_XCD_KSPLIT, TUNE_ATTN_XCD_HEADS, TUNE_GEMM_MID, TUNE_DECODER_FUSE, TUNE_ROW_GROUPS, TUNE_MHA_QTILE_WAVES = 0, 1, 2, 3, 4, 5      # PSALM_TUNE_* of include/psalm_hip.h
+    TUNE_PHI_ROPE_EPILOGUE = 6
 
     def set_tuning(self, key: int, value: int):
         """psalm_set_tuning: process-wide atomic switches between kernel forms with identical results (A/B runs, tests)."""
@@ -1223,6 +1249,41 @@ class Ops:
                                              heads, head_dim, rot, self._stream())
         self._check(rc, "psalm_causal_attention")
         return out
+
+    def causal_attention_workspace_bytes(self, B, L, heads):
+        self.lib.psalm_causal_attention_f32_workspace.restype = c_long
+        return self.lib.psalm_causal_attention_f32_workspace(B, L, heads)
+
+    def causal_attention_workspace(self, B, L, heads):
+        """The fp32 Phi attention's workspace, [Qr | Kr | Mk | Tk] (psalm_causal_attention_f32_workspace bytes): the one `causal_attention` and
+        `causal_attention_split` use for this shape, for the two-step form (phi_attention_tables, gemm_x3_split(rope=), causal_attention_split_prepared)."""
+        nbytes = self.causal_attention_workspace_bytes(B, L, heads)
+        key = ("causal_f32_ws", nbytes)
+        ws = self._ws.get(key)
+        if ws is None:
+            ws = self._ws[key] = torch.empty(nbytes, dtype=torch.uint8, device=self.device)
+        return ws
+
+    def phi_attention_tables(self, key_mask, ws, B, L, heads):
+        """psalm_phi_attention_tables: Mk / Tk of `ws` from key_mask (B, L) u8, zeros in the padding rows of Qr / Kr -- once per forward pass."""
+        if key_mask.dtype != torch.uint8 or key_mask.numel() != B * L or not key_mask.is_contiguous():
+            raise PsalmHipError("phi_attention_tables: contiguous uint8 key mask (B, L)")
+        if ws.dtype != torch.uint8 or ws.numel() < self.causal_attention_workspace_bytes(B, L, heads):
+            raise PsalmHipError("phi_attention_tables: workspace of causal_attention_workspace(B, L, heads)")
+        self._check(self.lib.psalm_phi_attention_tables(self._p(key_mask), self._p(ws), B, L, heads, self._stream()), "psalm_phi_attention_tables")
+
+    def causal_attention_split_prepared(self, buf, v_off, split_out, split_inv, split_col_off, ws, B, L, heads, head_dim):
+        """causal_attention_split's attention kernel alone, on a workspace whose Qr / Kr / Mk / Tk are in place (phi_attention_tables +
+        gemm_x3_split(rope=)); `buf` holds the v columns at v_off."""
+        if buf.dtype != torch.float32 or split_out.dtype != torch.float16 or split_inv.dtype != torch.float32:
+            raise PsalmHipError("causal_attention_split_prepared: float32 v buffer, float16 split buffer, float32 scales")
+        if ws.dtype != torch.uint8 or ws.numel() < self.causal_attention_workspace_bytes(B, L, heads):
+            raise PsalmHipError("causal_attention_split_prepared: workspace of causal_attention_workspace(B, L, heads)")
+        rc = self.lib.psalm_causal_attention_f32_split_prepared(self._pv(buf), c_long(buf.stride(0)), v_off, self._p(split_out),
+                                                                c_long(split_out.stride(0)), split_out.shape[1] // 2, split_col_off,
+                                                                self._p(split_inv), self._p(ws), B, L, heads, head_dim, self._stream())
+        self._check(rc, "psalm_causal_attention_f32_split_prepared")
+        return split_out
 
     def causal_attention_split(self, buf, q_off, k_off, v_off, split_out, split_inv, split_col_off, cos, sin, key_mask, B, L, heads,
                                head_dim, rot):
