@@ -44,8 +44,9 @@ const char* psalm_last_error(void);
  *    psalm_mask_nms, psalm_mask_paint_bits.
  * 15: connected components of binary planes: psalm_mask_components (+ _workspace), psalm_mask_clean (+ _workspace).
  * 16: RoPE in the [k|v|q|fc1] GEMM's epilogue: psalm_rope_out, psalm_gemm_x3_split_rope, psalm_phi_attention_tables,
- *    psalm_causal_attention_f32_split_prepared, psalm_phi_forward_plan, PSALM_TUNE_PHI_ROPE_EPILOGUE. */
-#define PSALM_ABI_VERSION 16
+ *    psalm_causal_attention_f32_split_prepared, psalm_phi_forward_plan, PSALM_TUNE_PHI_ROPE_EPILOGUE.
+ * 17: mask outlines and polygon fill: psalm_mask_outline_totals, psalm_mask_outlines (+ _workspace), psalm_mask_fill_polygons (+ _workspace). */
+#define PSALM_ABI_VERSION 17
 int psalm_abi_version(void);
 const char* psalm_backend(void); /* "hip-gfx950" */
 
@@ -901,6 +902,55 @@ int psalm_mask_components(const void* masks, int dtype_is_u8, int n, int H, int 
 long psalm_mask_clean_workspace(int m, int H, int W);
 int psalm_mask_clean(const void* masks, int dtype_is_u8, int n, int H, int W, const int* index_dev, int m, int connectivity, int min_island,
                      int max_hole, unsigned char* out, int* areas, int* filled, int* removed, void* workspace, long workspace_bytes, void* stream);
+
+/* ------------------------------------------------------------------------------------------------------------------
+ * Mask outlines and polygon fill (csrc/outlines.hip; psalm_amd/evalout.py mask_outlines / fill_polygons, PSALM.segment_everything(outlines=True),
+ * polygon prompts of image sessions).  Everything is integers.  Inputs follow psalm_mask_components: masks (n,H,W) contiguous, float32
+ * (dtype_is_u8 = 0; set when f > 0: NaN, -0.0 and negatives are not) or bytes (1; set when != 0); output row i is plane index_dev[i] (m entries,
+ * int32 on the device; an entry outside [0, n) is the EMPTY plane), or plane i when index_dev is NULL (then m must equal n); outside the plane is
+ * unset.  (H + 1) * (W + 1) * 4 < 2^31, m <= 65535.
+ *   Geometry: pixel (py, px) covers the square [px, px + 1] x [py, py + 1]; lattice vertices (x, y), 0 <= x <= W, 0 <= y <= H, x to the right, y
+ *     downwards.  A crack edge is a unit lattice segment with a set pixel on one side and an unset one on the other, directed so that the set pixel
+ *     is on its RIGHT (walking in +x the set pixel is the one below).  A vertex has 0, 1 or 2 outgoing edges (2 at a saddle: the 2 x 2 block around
+ *     it is set on exactly one diagonal) and as many incoming ones.
+ *   Successor of an edge at its end vertex: connectivity 8: the first existing of turn left, straight, turn right (left is counter-clockwise on
+ *     screen: heading +x, left is -y); connectivity 4: the first existing of right, straight, left.  Every edge has one successor and one
+ *     predecessor; the edges of a plane fall into disjoint closed RINGS.
+ *   A ring is output as its corner vertices (where the direction changes) in walking order, starting at its row-major lowest vertex (smallest y,
+ *     then x) -- always a corner, visited once, shared with no other ring of the plane.  The rings of a plane are ordered by that vertex.  The
+ *     signed area A = 1/2 sum (x_i y_i+1 - x_i+1 y_i) is an integer, positive for an outer boundary, negative for a hole; the areas of a plane add
+ *     up to its set pixels.
+ * Two steps, because the sizes of the result are data: the host reads psalm_mask_outline_totals' counts back (2 m small integers), sizes the
+ * tables and the work from them and calls psalm_mask_outlines -- on all m rows at once, or on row ranges whose workspace stays small; the tables'
+ * final row count is the sum of the ring counts.  Nothing proportional to H * W crosses the bus. */
+/* counts (3, m) i32, zeroed by the call: counts[0][i] = crack edges of output row i, counts[1][i] = its corners (the vertices its rings will
+ * hold), counts[2][i] = 0 (the ring counts psalm_mask_outlines fills in).  Local sums with integer add atomics; no workspace. */
+int psalm_mask_outline_totals(const void* masks, int dtype_is_u8, int n, int H, int W, const int* index_dev, int m, int* counts, void* stream);
+/* The output rows [row0, row0 + rows) of the same call (masks, index_dev, m and counts as given to psalm_mask_outline_totals; ranges are called
+ * in ascending order, on one stream).  edge_cap: a host-side bound on the edges of each of these planes (the largest of their counts[0]);
+ * it sizes the grids, the ceil(log2(edge_cap)) pointer-jumping rounds -- one launch per round, from one state array into the other -- and the
+ * workspace.  counts[2][row] receives the plane's ring count.
+ *   rings (ring_cap, 4) i32: row = [output row, first vertex offset, vertex count, signed area]; the planes in row order, a plane's rings in the
+ *     order above; a plane's first ring sits at the sum of the ring counts in front of it.  ring_cap >= sum(counts[1]) / 4 always suffices.
+ *   vertices (vertex_cap, 2) i32 = (x, y); vertices[a : a + k] flattened is a COCO polygon as it stands.  vertex_cap = sum(counts[1]) is exact.
+ * What does not fit ring_cap / vertex_cap is not written.  No kernel waits for another block or reads, within a launch, a word that another
+ * block writes in that launch; blocks combine with integer add atomics only: two calls give the same words.
+ * workspace: psalm_mask_outlines_workspace(rows, H, W, edge_cap) bytes (-1: bad arguments; 0 for edge_cap = 0), 16-byte aligned. */
+long psalm_mask_outlines_workspace(int m, int H, int W, int edge_cap);
+int psalm_mask_outlines(const void* masks, int dtype_is_u8, int n, int H, int W, const int* index_dev, int m, int row0, int rows, int connectivity,
+                        int edge_cap, int* counts, int* rings, int ring_cap, int* vertices, int vertex_cap, void* workspace, long workspace_bytes,
+                        void* stream);
+/* Even-odd fill over pixel centres of rings in the layout above -- psalm_mask_outlines' tables, or any integer polygons (a ring's vertex count
+ * >= 1; holes are simply rings; rings may cross themselves and each other) -> out (rows, H, W) bytes of 0 / 1 for the planes [row0, row0 + rows)
+ * (a ring whose plane lies outside the range, or whose vertex range leaves [0, V), is passed over).  Pixel (py, px) is set iff an odd number of
+ * non-horizontal ring edges, each taken with y0 < y1, satisfy
+ *     2 y0 <= 2 py + 1 < 2 y1   and   2 x0 (y1 - y0) + (2 py + 1 - 2 y0) (x1 - x0) > (2 px + 1) (y1 - y0)          (64-bit integers)
+ * i.e. cross the pixel centre's row strictly to its right; there are no ties to break.  One toggle per (edge, crossed row) with an integer add
+ * atomic, then a parity pass per row: O(edges * rows + H * W).  Vertices outside [0, W] x [0, H] are clipped consistently with the rule.
+ * workspace: psalm_mask_fill_polygons_workspace(rows, H, W) bytes (-1: bad arguments), 4-byte aligned; zeroed by the call itself. */
+long psalm_mask_fill_polygons_workspace(int m, int H, int W);
+int psalm_mask_fill_polygons(const int* rings, int R, const int* vertices, int V, int row0, int rows, int H, int W, unsigned char* out,
+                             void* workspace, long workspace_bytes, void* stream);
 
 #ifdef __cplusplus
 }

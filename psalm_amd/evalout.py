@@ -18,6 +18,9 @@ with one tiny RCCL all-reduce (`psalm_amd.dist.reduce_metrics`, the role of Aver
     mask_nms(masks, scores, iou_thr)              greedy mask NMS under an exact rational IoU threshold (PSALM.segment_everything's rule)
     mask_components(masks, connectivity)          a mask's connected parts as instances: labels in scipy.ndimage.label's numbering, count, box / area table
     clean_masks(masks, min_island, max_hole)      SAM-style post-processing: fill holes up to N pixels, then drop islands below N pixels
+    mask_outlines(masks, connectivity)            a mask's boundary as closed rings of lattice corners (COCO polygons as they stand), holes as rings
+    outline_polygons(out, holes)                  mask_outlines' tables on the host: per mask a list of flat [x0, y0, x1, y1, ...] lists
+    fill_polygons(rings, vertices, shape)         the way back: integer polygons -> masks, even-odd over pixel centres (fills an outline to its mask)
     coco_instance_records(instances, image_id)    detectron2 instances_to_coco_json (instance_evaluation.py) -> the COCO result records
 """
 from __future__ import annotations
@@ -305,11 +308,60 @@ def clean_masks(masks: torch.Tensor, min_island: int = 0, max_hole: int = 0, con
     return {"masks": out, "areas": areas, "removed": removed, "filled": filled}
 
 
-def coco_instance_records(instances, image_id, category_ids: Optional[Sequence[int]] = None, ops=None) -> List[dict]:
+def mask_outlines(masks: torch.Tensor, connectivity: int = 8, ops=None) -> dict:
+    """Masks as polygons -- what an annotation tool, a viewer's overlay or a COCO `segmentation` list wants -- traced on the device: masks (n,H,W)
+    float32 (set: > 0) | uint8 | bool (set: != 0), up to 65535, on host or device, (H + 1) * (W + 1) * 4 < 2^31 -> {"ring_count": (n) int32,
+    "vertex_count": (n) int32, "rings": (R,4) int32 = [mask, first vertex offset, vertex count, signed area], "vertices": (V,2) int32 = (x, y)}, on
+    the device.  Pixel (py, px) covers [px, px + 1] x [py, py + 1]; the boundary between set and unset pixels is walked with the set pixel on the
+    right and split into closed rings, joined at a diagonal contact under connectivity 8, separated under 4; a ring lists its corners only, from
+    its row-major lowest vertex; a mask's rings come in the order of those vertices.  area > 0: an outer boundary (as many as
+    `mask_components` counts), area < 0: a hole; a mask's areas add up to its pixels.  `fill_polygons` gives the masks back bit for bit.  Read
+    back: the per-mask edge / corner totals that size the work, and the ring counts -- nothing proportional to H * W."""
+    o = _ops(ops)
+    ring_count, vertex_count, rings, vertices = o.mask_outlines(_planes(o, masks, "mask_outlines"), connectivity=connectivity)
+    return {"ring_count": ring_count, "vertex_count": vertex_count, "rings": rings, "vertices": vertices}
+
+
+def outline_polygons(out: dict, holes: bool = False) -> List[List[List[int]]]:
+    """`mask_outlines`' result on the host: per mask a list of flat [x0, y0, x1, y1, ...] lists -- COCO polygons -- of its outer rings (area > 0),
+    or with holes=True of all its rings in table order.  Reads back the ring and vertex tables."""
+    n = int(out["ring_count"].shape[0])
+    rings = out["rings"].cpu().numpy()
+    verts = out["vertices"].cpu().numpy()
+    polys: List[List[List[int]]] = [[] for _ in range(n)]
+    for row, off, cnt, area in rings.tolist():
+        if holes or area > 0:
+            polys[row].append(verts[off:off + cnt].reshape(-1).tolist())
+    return polys
+
+
+def fill_polygons(rings, vertices, shape, ops=None) -> torch.Tensor:
+    """Integer polygons -> masks on the device: rings (R,4) int32 = [mask, first vertex offset, vertex count, anything], vertices (V,2) int32 =
+    (x, y) lattice points within [0, W] x [0, H] (tensors or arrays, host or device), shape = (m, H, W) -> (m,H,W) uint8 of 0 / 1.  Even-odd over
+    pixel centres: pixel (py, px) is set iff an odd number of ring edges cross the row y = py + 1/2 strictly right of x = px + 1/2 (in integers;
+    no ties).  Holes are rings; rings may cross; a ring given twice cancels.  `fill_polygons(out["rings"], out["vertices"], masks.shape)` of
+    `mask_outlines`' result is the masks' 0 / 1 planes."""
+    o = _ops(ops)
+    tabs = []
+    for t, cols, what in ((rings, 4, "rings"), (vertices, 2, "vertices")):
+        if not torch.is_tensor(t):
+            a = np.asarray(t)
+            t = torch.from_numpy(np.ascontiguousarray(a if a.size else np.zeros((0, cols), np.int32)))
+        if t.dim() != 2 or t.shape[1] != cols or t.dtype not in (torch.int32, torch.int64):
+            raise H.PsalmHipError(f"fill_polygons: {what} ({'RV'[cols == 2]},{cols}) integers, got {t.dtype} {tuple(t.shape)}")
+        tabs.append(t.to(torch.int32).to(o.device).contiguous())
+    return o.mask_fill_polygons(tabs[0], tabs[1], tuple(shape))
+
+
+def coco_instance_records(instances, image_id, category_ids: Optional[Sequence[int]] = None, ops=None, segmentation: str = "rle") -> List[dict]:
     """detectron2's `instances_to_coco_json`, the records the reference's instance evaluator collects (instance_evaluation.py): per instance
     {"image_id", "category_id", "bbox": [x, y, w, h] floats from `pred_boxes` (BoxMode XYXY_ABS -> XYWH_ABS), "score", "segmentation": COCO RLE
     with its counts as str}.  category_ids: the contiguous class index -> dataset category id table (the evaluator's reverse id mapping).
-    Only the small arrays (boxes, scores, classes, run boundaries) are read back; the boxes are real under `PSALM.mask_boxes = True`."""
+    Only the small arrays (boxes, scores, classes, run boundaries) are read back; the boxes are real under `PSALM.mask_boxes = True`.
+    segmentation="polygon": the COCO polygon form instead -- a list of flat [x0, y0, x1, y1, ...] lists, the outer rings of `mask_outlines`
+    (connectivity 8; COCO polygons cannot say holes: a consumer that fills them gets the mask with its holes closed)."""
+    if segmentation not in ("rle", "polygon"):
+        raise ValueError(f"coco_instance_records: segmentation = {segmentation!r} ('rle' or 'polygon')")
     n = len(instances)
     if n == 0:
         return []
@@ -318,10 +370,13 @@ def coco_instance_records(instances, image_id, category_ids: Optional[Sequence[i
     boxes[:, 3] -= boxes[:, 1]
     scores = instances.scores.detach().cpu().tolist()
     classes = instances.pred_classes.detach().cpu().tolist() if hasattr(instances, "pred_classes") else [0] * n
-    rles = masks_to_rle(instances.pred_masks, ops=ops)
+    if segmentation == "polygon":
+        polys = outline_polygons(mask_outlines(instances.pred_masks, ops=ops))
+    else:
+        rles = masks_to_rle(instances.pred_masks, ops=ops)
     out = []
     for k in range(n):
-        rle = {"size": rles[k]["size"], "counts": rles[k]["counts"].decode("utf-8")}
+        rle = polys[k] if segmentation == "polygon" else {"size": rles[k]["size"], "counts": rles[k]["counts"].decode("utf-8")}
         out.append({"image_id": image_id, "category_id": int(category_ids[classes[k]]) if category_ids is not None else int(classes[k]),
                     "bbox": boxes[k].tolist(), "score": float(scores[k]), "segmentation": rle})
     return out

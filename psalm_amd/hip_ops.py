@@ -49,7 +49,7 @@ def _dt(t: torch.Tensor) -> int:
         raise PsalmHipError(f"unsupported dtype {t.dtype} (float32 / bfloat16 only)")
 
 
-ABI_VERSION = 16       # == PSALM_ABI_VERSION of include/psalm_hip.h (tests/test_0_abi.py compares the two and the built library's answer)
+ABI_VERSION = 17       # == PSALM_ABI_VERSION of include/psalm_hip.h (tests/test_0_abi.py compares the two and the built library's answer)
 
 
 class _ProfiledLib:
@@ -2144,6 +2144,80 @@ class Ops:
                                            self._p(ws), c_long(nbytes), self._stream())
             self._check(rc, "psalm_mask_clean")
         return out, areas, filled, removed
+
+    # ------------------------------------------------------------------ mask outlines and polygon fill (csrc/outlines.hip)
+    def mask_outlines(self, masks, index=None, connectivity=8, max_workspace_bytes=None):
+        """masks (n,H,W) float32 (set: > 0) | uint8 / bool (set: != 0) -> (ring_count (m) i32, vertex_count (m) i32, rings (R,4) i32 = [output row,
+        first vertex offset, vertex count, signed area], vertices (V,2) i32 = (x, y)): psalm_mask_outline_totals + psalm_mask_outlines.  The crack
+        edges between set and unset pixels, directed with the set pixel on the right, joined at saddles by `connectivity`, as closed rings of
+        corner vertices; every ring starts at its row-major lowest vertex, a plane's rings are ordered by it; area > 0: an outer boundary, < 0: a
+        hole.  index (m) i32 on the device: the planes to outline (an entry outside [0, n) is the empty plane), default all n in order.
+        (H + 1) * (W + 1) * 4 < 2^31.  Two read-backs of small per-plane integers: the edge and corner totals that size the tables and the work,
+        and the ring counts that trim the ring table.  The rows are walked in chunks whose workspace (proportional to the planes' edges, plus five
+        bytes per lattice vertex) stays under max_workspace_bytes (default 256 MiB; at least one row per chunk): the result does not depend on it."""
+        masks, n, Hh, Ww, m = self._planes_args(masks, index, connectivity, "mask_outlines")
+        if (Hh + 1) * (Ww + 1) * 4 >= 1 << 31:
+            raise PsalmHipError(f"mask_outlines: planes of {Hh} x {Ww} pixels ((H + 1) * (W + 1) * 4 < 2^31)")
+        counts = self.empty(3, m, dtype=torch.int32)                  # [edges | vertices | rings] per output row
+        if m == 0:
+            return counts[2], counts[1], self.empty(0, 4, dtype=torch.int32), self.empty(0, 2, dtype=torch.int32)
+        u8 = 1 if masks.dtype == torch.uint8 else 0
+        rc = self.lib.psalm_mask_outline_totals(self._p(masks), u8, n, Hh, Ww, self._p(index), m, self._p(counts), self._stream())
+        self._check(rc, "psalm_mask_outline_totals")
+        edges, verts = counts[:2].cpu().numpy().astype(np.int64)      # read-back 1: 2 m small integers size everything below
+        V, cap = int(verts.sum()), int(edges.max())
+        if V >= 1 << 31:
+            raise PsalmHipError(f"mask_outlines: {V} vertices in one call (< 2^31): outline fewer planes at a time")
+        ring_cap = V // 4                                             # a ring has at least four corners
+        rings = self.empty(ring_cap, 4, dtype=torch.int32)
+        vertices = self.empty(V, 2, dtype=torch.int32)
+        if cap == 0:
+            return counts[2], counts[1], rings, vertices
+        ws_fn = self.lib.psalm_mask_outlines_workspace
+        ws_fn.restype = c_long
+
+        def per_rows(k, h, w):
+            return ws_fn(k, h, w, cap)
+        for r0, k, nbytes in self._plane_chunks(per_rows, m, Hh, Ww, max_workspace_bytes, "mask_outlines"):
+            ws = self._stage_ws("mask_outlines", max(nbytes, 16))
+            rc = self.lib.psalm_mask_outlines(self._p(masks), u8, n, Hh, Ww, self._p(index), m, r0, k, int(connectivity), int(edges[r0:r0 + k].max()),
+                                              self._p(counts), self._p(rings), ring_cap, self._p(vertices), V, self._p(ws), c_long(nbytes),
+                                              self._stream())
+            self._check(rc, "psalm_mask_outlines")
+        R = int(counts[2].cpu().numpy().astype(np.int64).sum())       # read-back 2: the ring counts trim the table
+        return counts[2], counts[1], rings[:R], vertices
+
+    def mask_fill_polygons(self, rings, vertices, shape, out=None, max_workspace_bytes=None, rows=None):
+        """rings (R,4) i32 = [plane, first vertex offset, vertex count, anything], vertices (V,2) i32 = (x, y) on the device, shape = (m, H, W) -> (m,H,W)
+        uint8 of 0 / 1: psalm_mask_fill_polygons, the even-odd fill over pixel centres.  The tables of mask_outlines give the planes back bit for bit;
+        any integer polygons in that layout are filled by the same rule (holes are rings; a ring given twice cancels).  A ring whose plane is
+        outside [0, m) or whose vertex range leaves the table is passed over.  `out` may be given (a view of a caller-owned block); chunked as
+        mask_components (one int32 per pixel of workspace).  rows = (first, k): only the planes [first, first + k) of the m are filled, into an
+        `out` of (k, H, W)."""
+        if not torch.is_tensor(rings) or rings.dim() != 2 or rings.shape[1] != 4:
+            raise PsalmHipError(f"mask_fill_polygons: rings (R,4) int32, got {tuple(getattr(rings, 'shape', ()))}")
+        if not torch.is_tensor(vertices) or vertices.dim() != 2 or vertices.shape[1] != 2:
+            raise PsalmHipError(f"mask_fill_polygons: vertices (V,2) int32, got {tuple(getattr(vertices, 'shape', ()))}")
+        R, V = int(rings.shape[0]), int(vertices.shape[0])
+        self._want(rings, torch.int32, (R, 4), "mask_fill_polygons rings")
+        self._want(vertices, torch.int32, (V, 2), "mask_fill_polygons vertices")
+        if not isinstance(shape, (tuple, list)) or len(shape) != 3 or any(isinstance(v, bool) or int(v) != v or int(v) < 0 for v in shape):
+            raise PsalmHipError(f"mask_fill_polygons: shape {shape!r} (m, H, W)")
+        m, Hh, Ww = (int(v) for v in shape)
+        if m > 65535 or (Hh + 1) * (Ww + 1) * 4 >= 1 << 31:
+            raise PsalmHipError(f"mask_fill_polygons: {m} planes of {Hh} x {Ww} pixels (at most 65535 planes, (H + 1) * (W + 1) * 4 < 2^31)")
+        first, m_out = (0, m) if rows is None else (int(rows[0]), int(rows[1]))
+        if not (0 <= first and 0 <= m_out and first + m_out <= m):
+            raise PsalmHipError(f"mask_fill_polygons: rows {rows!r} outside the {m} planes")
+        out = self.empty(m_out, Hh, Ww, dtype=torch.uint8) if out is None else self._want(out, torch.uint8, (m_out, Hh, Ww), "mask_fill_polygons out")
+        if m_out == 0 or Hh == 0 or Ww == 0:
+            return out
+        for r0, k, nbytes in self._plane_chunks(self.lib.psalm_mask_fill_polygons_workspace, m_out, Hh, Ww, max_workspace_bytes, "mask_fill_polygons"):
+            ws = self._stage_ws("mask_fill_polygons", max(nbytes, 4))
+            rc = self.lib.psalm_mask_fill_polygons(self._p(rings), R, self._p(vertices), V, first + r0, k, Hh, Ww, self._p(out[r0:r0 + k]), self._p(ws),
+                                                   c_long(nbytes), self._stream())
+            self._check(rc, "psalm_mask_fill_polygons")
+        return out
 
     def _iota(self, n):
         """0 .. n - 1 as int32 on the device (cached per length)"""

@@ -320,15 +320,17 @@ class SessionMixin:
     # validates and packs a primitive table; psalm_mask_rasterize / psalm_mask_dilate_disc / psalm_mask_resize_nearest_pad make the (S, S) region masks
     # the host path would have uploaded; ONE read-back brings the R pixel totals the sampler needs; psalm_mask_select_points turns its ranks into the
     # points `region_points` would have computed, bit for bit.
-    REGION_PROMPT_KEYS = ("points", "scribble", "box", "mask", "rle")
+    REGION_PROMPT_KEYS = ("points", "scribble", "box", "mask", "rle", "polygon")
     REGION_PROMPT_RADIUS = {"points": 10, "scribble": 5}              # coco_instance_mapper.py:247-250
     REGION_PROMPT_MAX_RADIUS = 16
+    REGION_POLYGON_MAX_VERTICES = 1 << 20                             # per call of _region_prompt_plan, all polygon prompts together
 
     def _region_prompt_plan(self, session, input_ids, seg_info, regions, tag="", transforms=None, canvas=None):
         """Host side of `regions=` for the N prompts of one session: validation (ValueError naming prompt and region) and the arrays that travel in
         the call's blob under names ending in `tag` -- the primitive table (n, 6) int32, the radii (R) int32 (-1: not dilated), host mask prompts,
-        the all-zero image index of region_pool.  R = all regions of the N prompts, prompt by prompt.  Without a session (`session=None`, the
-        video tracker): the image's geometry as `transforms` (its resize / pad record) and `canvas` (the (H, W) of the model's input)."""
+        the polygon prompts' ring (P, 4) and vertex (V, 2) tables in psalm_mask_fill_polygons' layout, the all-zero image index of region_pool.
+        R = all regions of the N prompts, prompt by prompt.  Without a session (`session=None`, the video tracker): the image's geometry as
+        `transforms` (its resize / pad record) and `canvas` (the (H, W) of the model's input)."""
         from .preprocess import rle_to_mask
         if self.seg_task != "region":
             raise ValueError(f"regions are prompts of the region task (this model's seg_task = {self.seg_task!r})")
@@ -348,6 +350,7 @@ class SessionMixin:
             raise ValueError(f"regions: one list of region prompts per prompt ({N} prompts)")
         n_tok = (input_ids == REGION_TOKEN_INDEX).sum(1).tolist()
         prims, radii, masks, counts = [], [], [], []
+        poly_rings, poly_verts, polys = [], [], []                # ring rows [region, first vertex, vertices, 0], vertices (x, y), the polygon regions
 
         def coord(v, what, where):
             if isinstance(v, (bool, np.bool_)) or not isinstance(v, (int, np.integer)):
@@ -396,6 +399,28 @@ class SessionMixin:
                         raise ValueError(f"{where}: box {(y0, x0, y1, x1)} is not 0 <= y0 < y1 <= {h}, 0 <= x0 < x1 <= {w}")
                     prims.append((g, 1, y0, x0, y1, x1))
                     radii.append(-1)
+                elif kind == "polygon":
+                    poly = rp["polygon"]
+                    if not isinstance(poly, (list, tuple, np.ndarray)) or len(poly) == 0:
+                        raise ValueError(f"{where}: a polygon is a ring [(y, x), ...] or a list of rings")
+                    first = poly[0]
+                    one_ring = isinstance(first, (list, tuple, np.ndarray)) and len(first) == 2 and not isinstance(first[0], (list, tuple, np.ndarray))
+                    for ring in ([poly] if one_ring else poly):
+                        if not isinstance(ring, (list, tuple, np.ndarray)) or len(ring) < 3:
+                            n_v = len(ring) if isinstance(ring, (list, tuple, np.ndarray)) else 0
+                            raise ValueError(f"{where}: a polygon ring of {n_v} vertices (at least 3)")
+                        poly_rings.append((g, len(poly_verts), len(ring), 0))
+                        for p in ring:
+                            if not isinstance(p, (list, tuple, np.ndarray)) or len(p) != 2:
+                                raise ValueError(f"{where}: {p!r} is not a (y, x) vertex")
+                            y, x = coord(p[0], "y", where), coord(p[1], "x", where)
+                            if not (0 <= y <= h and 0 <= x <= w):
+                                raise ValueError(f"{where}: vertex {(y, x)} outside the lattice 0..{h} x 0..{w} of the image of {(h, w)}")
+                            poly_verts.append((x, y))
+                        if len(poly_verts) > self.REGION_POLYGON_MAX_VERTICES:
+                            raise ValueError(f"{where}: the polygon prompts of one call hold more than {self.REGION_POLYGON_MAX_VERTICES} vertices")
+                    polys.append(g)
+                    radii.append(-1)
                 else:
                     m = rle_to_mask(rp["rle"]) if kind == "rle" else rp["mask"]
                     if not torch.is_tensor(m):
@@ -416,8 +441,11 @@ class SessionMixin:
         for g, m in masks:
             if not torch.is_tensor(m):
                 arrays[f"region_mask{tag}_{g}"] = m.reshape(-1)
+        if polys:
+            arrays[f"region_poly_rings{tag}"] = np.asarray(poly_rings, np.int32).reshape(-1)
+            arrays[f"region_poly_verts{tag}"] = np.asarray(poly_verts, np.int32).reshape(-1)
         return {"tag": tag, "R": R, "counts": counts, "hw": (h, w), "tables": (h, w, nh, nw, ph, pw), "masks": masks, "arrays": arrays,
-                "max_radius": max([0] + radii)}
+                "max_radius": max([0] + radii), "polygons": polys}
 
     def _region_prompt_masks(self, session, rp, dv, total, tables=None):
         """Device side, in front of the read-back: one launch each of rasterize, dilate and resize + pad for the R regions of `rp`; `total` (R) int32
@@ -438,6 +466,9 @@ class SessionMixin:
             else:
                 src = dv[f"region_mask{tag}_{g}"]
             o.copy_(raw[g], src.view(h, w))
+        for g in rp["polygons"]:                                  # polygon prompts: filled even-odd into their plane (psalm_mask_fill_polygons)
+            o.mask_fill_polygons(dv[f"region_poly_rings{tag}"].view(-1, 4), dv[f"region_poly_verts{tag}"].view(-1, 2), (R, h, w), rows=(g, 1),
+                                 out=raw[g:g + 1])
         dil = o.mask_dilate_disc(raw, dv[f"region_radii{tag}"], rp["max_radius"])
         return o.mask_resize_nearest_pad(dil, tabs[1], tabs[2], total=total)
 
@@ -473,7 +504,8 @@ class SessionMixin:
     def segment(self, session: "ImageSession", input_ids, attention_mask=None, *, seg_info=None, class_name_ids=None,
                 class_name_embedding_indices=None, cls_indices=None, token_refer_id=None, refer_embedding_indices=None, is_thing_list=None,
                 labels=None, region_point_sampler: Callable = default_region_point_sampler, postprocess: bool = True,
-                stages: Optional[dict] = None, regions=None, region_index_sampler: Callable = default_region_index_sampler, pick: bool = True):
+                stages: Optional[dict] = None, regions=None, region_index_sampler: Callable = default_region_index_sampler, pick: bool = True,
+                outlines: bool = False):
         """N >= 1 prompts of the model's task on the session's image: what `eval_seg` returns for a batch of N copies of that image with these
         prompts (a list of N result dicts), without running the vision side again and with a Phi pass over the rows behind the shared prefix
         only.  Prompt-side keywords as eval_seg; `seg_info`: per prompt (region masks / ground truth under "instances", geometry), default the
@@ -488,6 +520,9 @@ class SessionMixin:
             {"box": (y0, x0, y1, x1)}      half-open, 0 <= y0 < y1 <= h, 0 <= x0 < x1 <= w; not dilated
             {"mask": (h, w) uint8 / bool array or tensor, host or device}   used as it is (non-zero = set)
             {"rle": COCO RLE dict}         decoded on the host (preprocess.rle_to_mask), then a mask
+            {"polygon": [(y, x), ...]}     a ring of >= 3 integer LATTICE vertices, 0 <= y <= h, 0 <= x <= w (pixel (py, px) covers [py, py + 1] x
+                                           [px, px + 1]), or a list of such rings (holes are rings); filled even-odd over the pixel centres on the
+                                           device (psalm_mask_fill_polygons: the rule of evalout.fill_polygons); not dilated
         The prompt is drawn, dilated, resized + padded and sampled on the device (psalm_mask_rasterize, psalm_mask_dilate_disc,
         psalm_mask_resize_nearest_pad, psalm_mask_select_points: one launch each per call, one read-back of the R pixel totals);
         `region_index_sampler(m, n)` draws n ranks into the m pixels of a region, prompt by prompt, region by region.  The results equal, bit for
@@ -495,16 +530,19 @@ class SessionMixin:
         `region_point_sampler = lambda nz, k: region_index_sampler(nz.shape[0], k)`.  With `regions`, `gt` is returned only where the prompt's
         seg_info carries `instances.gt_masks`, and `pick=True` adds `picked_query` (R) int64, `picked_scores` (R) float32, `picked_masks`
         (R, H, W) uint8 (device tensors): per region the first arg-max of `instances.scores` and that query's mask -- and, with the model's
-        `mask_boxes` switch on, `picked_boxes` (R, 4) float32 / `picked_areas` (R) int32 of those masks."""
+        `mask_boxes` switch on, `picked_boxes` (R, 4) float32 / `picked_areas` (R) int32 of those masks.  `outlines=True` (with `pick`) adds
+        `picked_outlines`: evalout.mask_outlines of `picked_masks` (connectivity 8), the polygons of those masks as device tables."""
         kw = dict(input_ids=input_ids, attention_mask=attention_mask, seg_info=seg_info, class_name_ids=class_name_ids,
                   class_name_embedding_indices=class_name_embedding_indices, cls_indices=cls_indices, token_refer_id=token_refer_id,
                   refer_embedding_indices=refer_embedding_indices, is_thing_list=is_thing_list, regions=regions)
         return self._segment_requests([(session, kw)], grouped=False, postprocess=postprocess, stages=stages,
-                                      region_point_sampler=region_point_sampler, region_index_sampler=region_index_sampler, pick=pick)[0]
+                                      region_point_sampler=region_point_sampler, region_index_sampler=region_index_sampler, pick=pick,
+                                      outlines=outlines)[0]
 
     @torch.no_grad()
     def segment_many(self, requests, *, postprocess: bool = True, region_point_sampler: Callable = default_region_point_sampler,
-                     stages: Optional[dict] = None, region_index_sampler: Callable = default_region_index_sampler, pick: bool = True):
+                     stages: Optional[dict] = None, region_index_sampler: Callable = default_region_index_sampler, pick: bool = True,
+                     outlines: bool = False):
         """Prompts on SEVERAL images in one Phi pass: `requests` is a list of (session, kwargs) pairs, kwargs what `segment(session, **kwargs)` takes
         for the prompt side (input_ids, attention_mask, seg_info, class_name_ids, ..., is_thing_list).  Returns one list per request, each what
         `segment(session, **kwargs)` returns.  Every request obeys segment's rules on its own (session of this model and weights version, its
@@ -515,15 +553,15 @@ class SessionMixin:
         predictor and post-processing run per prompt from its own session.
         Region task: `region_point_sampler` is called request by request in list order, inside a request prompt by prompt and region by region --
         the order a loop of `segment` calls over `requests` draws in.
-        A request's kwargs may carry `regions` (and `pick`) as `segment` takes them: the prompt masks are made per request on the device, ONE read-back
+        A request's kwargs may carry `regions` (and `pick`, `outlines`) as `segment` takes them: the prompt masks are made per request on the device, ONE read-back
         brings the pixel totals of all requests, and `region_index_sampler` is called request by request, prompt by prompt, region by region.  Either
         every region request of a call gives `regions` or none does (the two paths draw from the sampler at different points of the call).
         `stages`: filled with the suffix rows' `inputs_embeds` / `hidden_states` ((N, S, hidden), N = all prompts in request order), `prefix_lens`
         (per prompt) and `lengths`."""
         return self._segment_requests(list(requests), grouped=True, postprocess=postprocess, stages=stages, region_point_sampler=region_point_sampler,
-                                      region_index_sampler=region_index_sampler, pick=pick)
+                                      region_index_sampler=region_index_sampler, pick=pick, outlines=outlines)
 
-    def _segment_requests(self, requests, *, grouped: bool, postprocess, stages, region_point_sampler, region_index_sampler, pick):
+    def _segment_requests(self, requests, *, grouped: bool, postprocess, stages, region_point_sampler, region_index_sampler, pick, outlines=False):
         """The one pipeline behind `segment` (grouped = False: its one request) and `segment_many` (grouped = True): a list of (session, kwargs)
         pairs -> one list of results per request.  Per request: validation, the region prompts' host side, the suffix splice plan; then the
         prefix caches (one per session), ONE blob with the suffix plans side by side, the region masks / points / features, ONE Phi suffix pass,
@@ -709,6 +747,9 @@ class SessionMixin:
                     res = self._postprocess(res, self._post_sizes(Hi, Wi, seg_info[b], cfg.size_divisibility))
                     picked = self._region_pick(res) if rps[ri] is not None and requests[ri][1].get("pick", pick) and n_regions[b] else {}
                     res = self._finalize(res, seg_info[b], gt_optional=rps[ri] is not None)
+                    if picked and requests[ri][1].get("outlines", outlines):
+                        from .evalout import mask_outlines
+                        picked["picked_outlines"] = mask_outlines(picked["picked_masks"], connectivity=8, ops=o)
                     res.update(picked)
                 outs.append(res)
             results.append(outs)
@@ -718,7 +759,7 @@ class SessionMixin:
     def segment_everything(self, session: "ImageSession", input_ids, attention_mask=None, *, grid=(8, 8), regions=None, radius=None,
                            iou_thr=0.7, min_area: int = 1, min_score: Optional[float] = None,
                            region_index_sampler: Callable = default_region_index_sampler, min_island: int = 0, max_hole: int = 0,
-                           connectivity: int = 8):
+                           connectivity: int = 8, outlines: bool = False):
         """"Show me all the objects": a grid of clicks on the session's image, one mask per object back.  `input_ids` (N, T): region-task prompts
         on the session's image that hold R <region> tokens together, 1 <= R <= 1024.  Either `grid=(gy, gx)` with gy * gx == R -- one click per
         cell at the cell centre ((2 i + 1) h // (2 gy), (2 j + 1) w // (2 gx)) of the original (h, w), dealt to the prompts in row-major order by
@@ -741,7 +782,11 @@ class SessionMixin:
         complementary connectivity, are filled; then islands of fewer than min_island pixels under `connectivity` are dropped) and everything
         above -- pair counts, NMS with `min_area` on the cleaned area, the label map, `masks`, `areas`, `boxes` -- describes the cleaned masks;
         the result gains `cleaned` (R, 2) int32 = [removed, filled] pixels per click.  With both 0 the call is launch for launch the one
-        without them."""
+        without them.
+
+        `outlines=True`: the result gains `outlines`, evalout.mask_outlines of the K returned `masks` under the call's `connectivity` -- the
+        survivors as polygons (`evalout.outline_polygons` lists them; COCO `segmentation` lists as they stand) -- behind everything else: every
+        other key and every launch in front of it are those of the call without it."""
         from .evalout import iou_fraction
         if self.seg_task != "region":
             raise ValueError(f"segment_everything: clicks are prompts of the region task (this model's seg_task = {self.seg_task!r})")
@@ -785,14 +830,16 @@ class SessionMixin:
         kw = dict(input_ids=input_ids, attention_mask=attention_mask, regions=regions)
         prompts = self._segment_requests([(session, kw)], grouped=False, postprocess=True, stages=None,
                                          region_point_sampler=default_region_point_sampler, region_index_sampler=region_index_sampler, pick=True)[0]
-        out = self._everything_dedup(prompts, n_tok, num, den, min_area, min_score, int(min_island), int(max_hole), int(connectivity))
+        out = self._everything_dedup(prompts, n_tok, num, den, min_area, min_score, int(min_island), int(max_hole), int(connectivity),
+                                     outlines=bool(outlines))
         out["prompts"] = prompts
         return out
 
-    def _everything_dedup(self, prompts, n_tok, num, den, min_area, min_score, min_island=0, max_hole=0, connectivity=8):
+    def _everything_dedup(self, prompts, n_tok, num, den, min_area, min_score, min_island=0, max_hole=0, connectivity=8, outlines=False):
         """The device step behind the pipeline: `prompts`, what `segment(..., pick=True)` returned for prompts of n_tok[b] regions each ->
         segment_everything's result without "prompts".  Reads `instances.pred_masks`, `picked_query` and `picked_scores` of every prompt.
-        min_island / max_hole > 0: the picked planes are cleaned (psalm_mask_clean) into one (R, H, W) byte buffer, which is packed instead."""
+        min_island / max_hole > 0: the picked planes are cleaned (psalm_mask_clean) into one (R, H, W) byte buffer, which is packed instead.
+        outlines: behind everything else, the K survivors' masks as polygons (evalout.mask_outlines under `connectivity`)."""
         o = self.ops
         R = int(sum(n_tok))
         sizes = {tuple(p["instances"].pred_masks.shape[1:]) for p in prompts}
@@ -838,4 +885,7 @@ class SessionMixin:
                "labels": labels, "owner": o.to_i64(owner), "keep": keep}
         if clean:
             out["cleaned"] = cleaned.t().contiguous()
+        if outlines:
+            from .evalout import mask_outlines
+            out["outlines"] = mask_outlines(masks, connectivity=connectivity, ops=o)
         return out
