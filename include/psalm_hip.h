@@ -45,8 +45,9 @@ const char* psalm_last_error(void);
  * 15: connected components of binary planes: psalm_mask_components (+ _workspace), psalm_mask_clean (+ _workspace).
  * 16: RoPE in the [k|v|q|fc1] GEMM's epilogue: psalm_rope_out, psalm_gemm_x3_split_rope, psalm_phi_attention_tables,
  *    psalm_causal_attention_f32_split_prepared, psalm_phi_forward_plan, PSALM_TUNE_PHI_ROPE_EPILOGUE.
- * 17: mask outlines and polygon fill: psalm_mask_outline_totals, psalm_mask_outlines (+ _workspace), psalm_mask_fill_polygons (+ _workspace). */
-#define PSALM_ABI_VERSION 17
+ * 17: mask outlines and polygon fill: psalm_mask_outline_totals, psalm_mask_outlines (+ _workspace), psalm_mask_fill_polygons (+ _workspace).
+ * 18: mask distance maps: psalm_mask_distance (+ _workspace), psalm_mask_centers, psalm_mask_boundaries, psalm_boundary_counts (+ _workspace). */
+#define PSALM_ABI_VERSION 18
 int psalm_abi_version(void);
 const char* psalm_backend(void); /* "hip-gfx950" */
 
@@ -951,6 +952,54 @@ int psalm_mask_outlines(const void* masks, int dtype_is_u8, int n, int H, int W,
 long psalm_mask_fill_polygons_workspace(int m, int H, int W);
 int psalm_mask_fill_polygons(const int* rings, int R, const int* vertices, int V, int row0, int rows, int H, int W, unsigned char* out,
                              void* workspace, long workspace_bytes, void* stream);
+
+/* ------------------------------------------------------------------------------------------------------------------
+ * Mask distance maps (csrc/distance.hip; psalm_amd/evalout.py mask_distance / mask_centers / mask_boundaries / boundary_counts,
+ * PSALM.segment_everything(centers=True)): how far each pixel is from the mask's edge, the click deepest inside a mask, the boundary half of
+ * DAVIS's J&F.  Everything is integers.  Inputs follow psalm_mask_components: masks (n,H,W) contiguous, float32 (dtype_is_u8 = 0; set when f > 0:
+ * NaN, -0.0 and negatives are not) or bytes (1; set when != 0); output row i is plane index_dev[i] (m entries, int32 on the device; an entry
+ * outside [0, n) is the EMPTY plane), or plane i when index_dev is NULL (then m must equal n).  1 <= H, W <= 16384 (so that every true squared
+ * distance is below FAR = 2^30), m <= 65535, m == 0 is a no-op.  Nothing allocates or synchronises; workspaces are caller-owned, 256-byte aligned
+ * and written by a call before it reads them: nothing depends on what they held. */
+/* dist2 (m,H,W) i32: dist2[y][x] = min over the seed pixels (y', x') of (y - y')^2 + (x - x')^2.
+ *   to_set = 0: the seeds are the UNSET pixels (the inside distance: scipy.ndimage.distance_transform_edt(mask) squared; unset pixels get 0);
+ *   to_set = 1: the seeds are the SET pixels (distance_transform_edt(~mask) squared).
+ *   border = 1: every position outside the image is a seed too: the result is the min of the above and min(y + 1, H - y, x + 1, W - x)^2 -- the
+ *               transform of the plane padded with seeds all round, cropped back.
+ *   A plane without a seed (and border = 0) gives FAR = 2^30 everywhere.
+ * Exact and separable (Saito-Toriwaki / Meijster), two launches: a wavefront per row turns 64 pixels into a ballot word and takes the nearest
+ * seed left / right from leading / trailing zero counts with a carry across words (uint16 row distances); a lane per column builds the lower
+ * envelope of the column's parabolas in integers (stacks in the workspace, laid out [depth][column]) and reads it off.  O(H * W) per plane
+ * whatever it holds.  No block reads what another block of the same launch writes.
+ * workspace: psalm_mask_distance_workspace(m, H, W) bytes (-1: bad arguments): per pixel a uint16 row distance and two uint16 stack entries. */
+long psalm_mask_distance_workspace(int m, int H, int W);
+int psalm_mask_distance(const void* masks, int dtype_is_u8, int n, int H, int W, const int* index_dev, int m, int to_set, int border, int* dist2,
+                        void* workspace, long workspace_bytes, void* stream);
+/* centers (m,3) i32 = [y, x, dist2[y][x]] of the set pixel of each plane with the largest dist2 -- given psalm_mask_distance(to_set = 0,
+ * border = 1) of the SAME planes (same masks, index_dev, m), the pixel deepest inside: every pixel with (y' - y)^2 + (x' - x)^2 < dist2 is inside
+ * the image and set.  Ties go to the lowest row-major index; [-1, -1, 0] for a plane without a set pixel.  One pass: per block the maximum of
+ * (dist2 << 32) | (0xFFFFFFFF - flat index), one 64-bit atomicMax per block into slots[row] (the key decides, not the order of arrival), then a
+ * decode launch.  slots: m 64-bit words, 8-byte aligned, zeroed by the call. */
+int psalm_mask_centers(const void* masks, int dtype_is_u8, int n, int H, int W, const int* index_dev, int m, const int* dist2,
+                       unsigned long long* slots, int* centers, void* stream);
+/* out (m,H,W) bytes of 0 / 1: the boundary map of DAVIS's seg2bmap at the plane's own size.  With e[y][x] = m[y][x + 1], s[y][x] = m[y + 1][x],
+ * se[y][x] = m[y + 1][x + 1]: b = (m ^ e) | (m ^ s) | (m ^ se) for y < H - 1, x < W - 1; b[H - 1][x] = m ^ e for x < W - 1; b[y][W - 1] = m ^ s for
+ * y < H - 1; b[H - 1][W - 1] = 0. */
+int psalm_mask_boundaries(const void* masks, int dtype_is_u8, int n, int H, int W, const int* index_dev, int m, unsigned char* out, void* stream);
+/* DAVIS's f_measure in integers.  The mp prediction planes (pred, pred_index_dev as above) and the mt target planes (gt, gt_index_dev) get their
+ * boundary maps and the "within `bound` pixels of that boundary" maps (psalm_mask_distance's passes with the boundary pixels as seeds, no
+ * border, thresholded at bound^2) ONCE per plane; then for pair k = (pair_pred[k], pair_gt[k]) -- P int32 each, on the device, indices into the
+ * mp / mt planes; a pair with an index outside them counts nothing --
+ *   counts (P,4) i64, zeroed by the call = [n_fg, n_gt, fg_match, gt_match]: the boundary pixels of the prediction and of the target, the
+ *   prediction boundary pixels whose squared distance to the target's boundary is <= bound^2, and the mirror image.
+ * That is cv2.dilate(boundary, disk(bound)) with the disc dy^2 + dx^2 <= bound^2; nothing is added at the image border.  0 <= bound <= 32767,
+ * P <= 65535, mp + mt <= 65535.  Void pixels are not modelled.
+ * workspace: psalm_boundary_counts_workspace(mp, mt, H, W) bytes (-1: bad arguments): two bytes per pixel of the mp + mt planes and the
+ * distance passes' own workspace for as many planes as 64 MiB hold (the passes run on such groups in stream order). */
+long psalm_boundary_counts_workspace(int mp, int mt, int H, int W);
+int psalm_boundary_counts(const void* pred, int pred_is_u8, int n_pred, const int* pred_index_dev, int mp, const void* gt, int gt_is_u8, int n_gt,
+                          const int* gt_index_dev, int mt, int H, int W, const int* pair_pred, const int* pair_gt, int P, int bound,
+                          long long* counts, void* workspace, long workspace_bytes, void* stream);
 
 #ifdef __cplusplus
 }

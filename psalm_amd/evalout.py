@@ -21,10 +21,16 @@ with one tiny RCCL all-reduce (`psalm_amd.dist.reduce_metrics`, the role of Aver
     mask_outlines(masks, connectivity)            a mask's boundary as closed rings of lattice corners (COCO polygons as they stand), holes as rings
     outline_polygons(out, holes)                  mask_outlines' tables on the host: per mask a list of flat [x0, y0, x1, y1, ...] lists
     fill_polygons(rings, vertices, shape)         the way back: integer polygons -> masks, even-odd over pixel centres (fills an outline to its mask)
+    mask_distance(masks, to, border)              exact squared Euclidean distance maps (scipy distance_transform_edt squared) of masks on the device
+    mask_centers(masks)                           a click from a mask: the set pixel deepest inside, [y, x, dist2] per mask
+    mask_boundaries(masks)                        DAVIS seg2bmap at the mask's own size
+    boundary_counts(pred, gt, pairs, bound)       DAVIS f_measure's integers per pair; boundary_f(counts) -> precision, recall, F; davis_bound(shape)
+    JFMeters                                      DAVIS J&F bookkeeping beside IoUMeters (J from iou_counts, F from boundary_counts) + all-reduce
     coco_instance_records(instances, image_id)    detectron2 instances_to_coco_json (instance_evaluation.py) -> the COCO result records
 """
 from __future__ import annotations
 
+import math
 from ctypes import c_long
 from typing import List, Optional, Sequence, Tuple
 
@@ -353,6 +359,79 @@ def fill_polygons(rings, vertices, shape, ops=None) -> torch.Tensor:
     return o.mask_fill_polygons(tabs[0], tabs[1], tuple(shape))
 
 
+def mask_distance(masks: torch.Tensor, to: str = "unset", border: bool = False, ops=None) -> torch.Tensor:
+    """How far each pixel is from the mask's edge, exactly: masks (n,H,W) float32 (set: > 0) | uint8 | bool (set: != 0), up to 65535, on host or
+    device, 1 <= H, W <= 16384 -> (n,H,W) int32 on the device, the SQUARED Euclidean distance to the nearest seed pixel.  to="unset": the seeds are
+    the unset pixels -- the inside distance, `scipy.ndimage.distance_transform_edt(mask) ** 2`, 0 off the mask; to="set": the set pixels,
+    `distance_transform_edt(~mask) ** 2`.  border=True: every position outside the image is a seed too (the transform of the plane padded with
+    seeds all round, cropped back).  A plane without any seed gives 2^30 everywhere.  `dist2 <= r * r` erodes (to="unset") or dilates (to="set")
+    by a disc of any radius; `dist2.amax()` is how thick a mask is.  Nothing is read back."""
+    o = _ops(ops)
+    return o.mask_distance(_planes(o, masks, "mask_distance"), to=to, border=border)
+
+
+def mask_centers(masks: torch.Tensor, ops=None) -> torch.Tensor:
+    """A click from a mask -- the point every interactive tool uses: masks (n,H,W) as `mask_distance` takes them -> (n,3) int32 on the device =
+    [y, x, dist2] of the set pixel deepest inside, the first maximum (row-major) of `mask_distance(masks, border=True)` over the set pixels, the
+    image border counted as outside; [-1, -1, 0] for an empty mask.  Every pixel with (y' - y)^2 + (x' - x)^2 < dist2 is inside the image and
+    set.  (y, x) is a valid {"points": [(y, x)]} prompt for `segment` / `VideoTracker.start` when the masks are in the original image's pixels.
+    Nothing is read back."""
+    o = _ops(ops)
+    return o.mask_centers(_planes(o, masks, "mask_centers"))
+
+
+def mask_boundaries(masks: torch.Tensor, ops=None) -> torch.Tensor:
+    """DAVIS's `seg2bmap` at the mask's own size: masks (n,H,W) as `mask_distance` takes them -> (n,H,W) uint8 of 0 / 1 on the device: a pixel
+    that differs from its right, lower or lower-right neighbour (the last row looks right only, the last column down only, the last pixel is
+    0).  Nothing is read back."""
+    o = _ops(ops)
+    return o.mask_boundaries(_planes(o, masks, "mask_boundaries"))
+
+
+def davis_bound(shape, bound_th: float = 0.008) -> int:
+    """DAVIS's boundary tolerance in pixels for masks of `shape` = (H, W): `bound_th` itself if >= 1, else ceil(bound_th * hypot(H, W))."""
+    Hh, Ww = int(shape[-2]), int(shape[-1])
+    return int(bound_th) if bound_th >= 1 else int(math.ceil(bound_th * math.hypot(Hh, Ww)))
+
+
+def boundary_counts(pred_masks: torch.Tensor, gt_masks: torch.Tensor, pairs: Sequence[Tuple[int, int]], bound: int, ops=None) -> torch.Tensor:
+    """The integers of DAVIS's boundary measure F (`f_measure`, without void pixels) for each (prediction index, target index) pair, on the
+    device: pred_masks (n,H,W), gt_masks (m,H,W) as `mask_distance` takes them, `bound` an integer number of pixels, 0 <= bound <= 32767
+    (`davis_bound(shape)`) -> (P,4) int64 = [n_fg, n_gt, fg_match, gt_match]: the boundary pixels (`mask_boundaries`) of the prediction and of
+    the target, the prediction boundary pixels within `bound` of the target's boundary (dy^2 + dx^2 <= bound^2, the disc of
+    `cv2.dilate(., disk(bound))`), and the mirror image.  Only the planes the pairs name are processed, each once.  `boundary_f` turns the
+    counts into precision, recall and F.  Nothing is read back."""
+    o = _ops(ops)
+    pred_masks = _planes(o, pred_masks, "boundary_counts")
+    gt_masks = _planes(o, gt_masks, "boundary_counts")
+    if tuple(pred_masks.shape[1:]) != tuple(gt_masks.shape[1:]):
+        raise H.PsalmHipError(f"boundary_counts: predictions of {tuple(pred_masks.shape[1:])} against targets of {tuple(gt_masks.shape[1:])}")
+    n, m = int(pred_masks.shape[0]), int(gt_masks.shape[0])
+    pairs = [(int(p), int(t)) for p, t in pairs]
+    if any(not (0 <= p < n and 0 <= t < m) for p, t in pairs):
+        raise H.PsalmHipError(f"boundary_counts: pair index out of range (predictions {n}, targets {m})")
+    up, ut = sorted({p for p, _ in pairs}), sorted({t for _, t in pairs})
+    rp, rt = {p: i for i, p in enumerate(up)}, {t: i for i, t in enumerate(ut)}
+    tab = torch.tensor(up + ut + [rp[p] for p, _ in pairs] + [rt[t] for _, t in pairs], dtype=torch.int32).to(o.device)      # one small upload
+    a, b, P = len(up), len(up) + len(ut), len(pairs)
+    return o.boundary_counts(pred_masks, gt_masks, tab[b:b + P], tab[b + P:], bound, pred_index=tab[:a], gt_index=tab[a:b])
+
+
+def boundary_f(counts) -> Tuple[np.ndarray, np.ndarray, np.ndarray]:
+    """`boundary_counts`' (P,4) integers -> (precision, recall, F), float64 arrays on the host, with DAVIS's special cases: no prediction
+    boundary but a target one: P = 1, R = 0; the reverse: P = 0, R = 1; neither: P = R = 1; else P = fg_match / n_fg, R = gt_match / n_gt;
+    F = 0 if P + R == 0 else 2 P R / (P + R).  Reads back the 4 P integers."""
+    c = (counts.cpu().numpy() if torch.is_tensor(counts) else np.asarray(counts)).astype(np.int64).reshape(-1, 4)
+    n_fg, n_gt, fg_m, gt_m = (c[:, k].astype(np.float64) for k in range(4))
+    prec = np.where(n_fg > 0, fg_m / np.maximum(n_fg, 1), 1.0)
+    rec = np.where(n_gt > 0, gt_m / np.maximum(n_gt, 1), 1.0)
+    prec = np.where((n_fg > 0) & (n_gt == 0), 0.0, prec)
+    rec = np.where((n_fg == 0) & (n_gt > 0), 0.0, rec)
+    s = prec + rec
+    f = np.where(s == 0, 0.0, 2 * prec * rec / np.where(s == 0, 1.0, s))
+    return prec, rec, f
+
+
 def coco_instance_records(instances, image_id, category_ids: Optional[Sequence[int]] = None, ops=None, segmentation: str = "rle") -> List[dict]:
     """detectron2's `instances_to_coco_json`, the records the reference's instance evaluator collects (instance_evaluation.py): per instance
     {"image_id", "category_id", "bbox": [x, y, w, h] floats from `pred_boxes` (BoxMode XYXY_ABS -> XYWH_ABS), "score", "segmentation": COCO RLE
@@ -414,6 +493,43 @@ class IoUMeters:
         ciou = float(self.sum[1] / (self.sum[3] + 1e-10))      # iou_class[1], region_segmentation.py:286-287
         giou = float(self.sum[5] / max(float(self.sum[6]), 1e-5))
         return {"ciou": ciou, "giou": giou, "n": int(self.sum[6])}
+
+
+class JFMeters:
+    """DAVIS's J&F beside `IoUMeters`: per (prediction, target) pair J = intersection / union of the foreground (1 where the union is empty)
+    and F = `boundary_f` of the pair's `boundary_counts`; `results()` gives their means over the pairs seen, `all_reduce()` sums the meters
+    over ranks as ONE small all-reduce (`psalm_amd.dist.reduce_metrics`)."""
+
+    def __init__(self):
+        self.sum = torch.zeros(3, dtype=torch.float64)         # [sum J, sum F, n]
+
+    def update(self, inter: torch.Tensor, union: torch.Tensor, bcounts: torch.Tensor) -> None:
+        """inter / union: (P) foreground pixel counts, or the (P,2) tensors of `iou_counts` (the foreground column is taken); bcounts (P,4) of
+        `boundary_counts` for the same pairs."""
+        i, u = inter.double().cpu(), union.double().cpu()
+        if i.dim() == 2:
+            i, u = i[:, 1], u[:, 1]
+        j = torch.where(u == 0, torch.ones_like(u), i / torch.where(u == 0, torch.ones_like(u), u))
+        f = boundary_f(bcounts)[2]
+        if f.shape[0] != j.shape[0]:
+            raise ValueError(f"JFMeters.update: {j.shape[0]} overlap counts against {f.shape[0]} boundary counts")
+        self.sum[0] += j.sum()
+        self.sum[1] += float(f.sum())
+        self.sum[2] += j.shape[0]
+
+    def all_reduce(self, device=None) -> None:
+        """SUM over ranks, as IoUMeters.all_reduce."""
+        import torch.distributed as dist
+        from .dist import reduce_metrics
+        if device is None and dist.is_available() and dist.is_initialized() and dist.get_backend() == "nccl":
+            device = torch.device("cuda", torch.cuda.current_device())
+        t = self.sum.to(device) if device is not None else self.sum.clone()
+        self.sum = reduce_metrics(t).double().cpu()
+
+    def results(self) -> dict:
+        n = max(float(self.sum[2]), 1.0)
+        j, f = float(self.sum[0]) / n, float(self.sum[1]) / n
+        return {"J": j, "F": f, "J&F": (j + f) / 2, "n": int(self.sum[2])}
 
 
 def compact_results(result: dict, gt_sem: Optional[torch.Tensor] = None, conf: Optional[ConfusionMatrix] = None, ops=None) -> dict:

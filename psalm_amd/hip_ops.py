@@ -49,7 +49,7 @@ def _dt(t: torch.Tensor) -> int:
         raise PsalmHipError(f"unsupported dtype {t.dtype} (float32 / bfloat16 only)")
 
 
-ABI_VERSION = 17       # == PSALM_ABI_VERSION of include/psalm_hip.h (tests/test_0_abi.py compares the two and the built library's answer)
+ABI_VERSION = 18       # == PSALM_ABI_VERSION of include/psalm_hip.h (tests/test_0_abi.py compares the two and the built library's answer)
 
 
 class _ProfiledLib:
@@ -2218,6 +2218,139 @@ class Ops:
                                                    c_long(nbytes), self._stream())
             self._check(rc, "psalm_mask_fill_polygons")
         return out
+
+    # ------------------------------------------------------------------ mask distance maps (csrc/distance.hip)
+    DISTANCE_MAX_SIDE = 16384
+    DISTANCE_FAR = 1 << 30
+    BOUNDARY_MAX_BOUND = 32767
+
+    def _distance_args(self, masks, index, what):
+        """masks (n,H,W) float32 / uint8 / bool, 1 <= H, W <= 16384, at most 65535 output rows -> (masks as the kernels read them, n, H, W, m)"""
+        if not torch.is_tensor(masks) or masks.dim() != 3 or masks.dtype not in (torch.float32, torch.uint8, torch.bool):
+            raise PsalmHipError(f"{what}: masks (n,H,W) float32 / uint8 / bool, got {getattr(masks, 'dtype', type(masks))} "
+                                f"{tuple(getattr(masks, 'shape', ()))}")
+        if masks.dtype == torch.bool:
+            masks = masks.view(torch.uint8)
+        n, Hh, Ww = (int(v) for v in masks.shape)
+        if not (1 <= Hh <= self.DISTANCE_MAX_SIDE and 1 <= Ww <= self.DISTANCE_MAX_SIDE):
+            raise PsalmHipError(f"{what}: planes of {Hh} x {Ww} pixels (1 <= H, W <= {self.DISTANCE_MAX_SIDE})")
+        m = n if index is None else int(index.numel())
+        if index is not None:
+            self._want(index, torch.int32, (m,), f"{what} index")
+        if m > 65535:
+            raise PsalmHipError(f"{what}: {m} output rows (at most 65535)")
+        return masks, n, Hh, Ww, m
+
+    def _aligned_ws(self, name, nbytes):
+        """_stage_ws, cut to start on a 256-byte boundary (the distance entries ask for it; the host allocator of the emulation gives 64)"""
+        t = self._stage_ws(name, nbytes + 256)
+        off = (-t.data_ptr()) % 256
+        return t[off:off + nbytes]
+
+    def mask_distance(self, masks, index=None, to="unset", border=False, out=None, max_workspace_bytes=None):
+        """masks (n,H,W) float32 (set: > 0) | uint8 / bool (set: != 0) -> dist2 (m,H,W) i32, the exact squared Euclidean distance of every pixel to the
+        nearest seed pixel: psalm_mask_distance.  to="unset": the seeds are the unset pixels (the inside distance, 0 off the mask); to="set": the set
+        pixels.  border=True: every position outside the image is a seed too.  DISTANCE_FAR = 2^30 where there is no seed at all.  index (m) i32 on
+        the device: the planes to transform (an entry outside [0, n) is the empty plane), default all n in order.  1 <= H, W <= 16384.  `out` may
+        be given; the rows are walked in chunks whose workspace (six bytes per pixel) stays under max_workspace_bytes (default 256 MiB; at least
+        one row per chunk): the result does not depend on it."""
+        masks, n, Hh, Ww, m = self._distance_args(masks, index, "mask_distance")
+        if to not in ("unset", "set"):
+            raise PsalmHipError(f"mask_distance: to = {to!r} ('unset': distance to the unset pixels, or 'set')")
+        if not isinstance(border, (bool, np.bool_)):
+            raise PsalmHipError(f"mask_distance: border = {border!r} (True or False)")
+        out = self.empty(m, Hh, Ww, dtype=torch.int32) if out is None else self._want(out, torch.int32, (m, Hh, Ww), "mask_distance out")
+        if m == 0:
+            return out
+        chunks = self._plane_chunks(self.lib.psalm_mask_distance_workspace, m, Hh, Ww, max_workspace_bytes, "mask_distance")
+        if index is None and len(chunks) > 1:
+            index = self._iota(n)
+        for r0, k, nbytes in chunks:
+            ws = self._aligned_ws("mask_distance", nbytes)
+            rc = self.lib.psalm_mask_distance(self._p(masks), 1 if masks.dtype == torch.uint8 else 0, n, Hh, Ww,
+                                              self._p(index[r0:r0 + k]) if index is not None else c_void_p(0), k, 1 if to == "set" else 0,
+                                              1 if border else 0, self._p(out[r0:r0 + k]), self._p(ws), c_long(nbytes), self._stream())
+            self._check(rc, "psalm_mask_distance")
+        return out
+
+    def mask_centers(self, masks, index=None, dist2=None, out=None, max_workspace_bytes=None):
+        """masks (n,H,W) float32 | uint8 / bool -> centers (m,3) i32 = [y, x, dist2] of each plane's set pixel deepest inside -- the first maximum, in
+        row-major order, of mask_distance(to="unset", border=True) over the set pixels; [-1, -1, 0] for an empty plane: psalm_mask_centers.  dist2
+        (m,H,W) i32: that map when the caller has it; otherwise it is made here, chunk by chunk (ten bytes per pixel under max_workspace_bytes,
+        default 256 MiB), and dropped."""
+        masks, n, Hh, Ww, m = self._distance_args(masks, index, "mask_centers")
+        out = self.empty(m, 3, dtype=torch.int32) if out is None else self._want(out, torch.int32, (m, 3), "mask_centers out")
+        if dist2 is not None:
+            self._want(dist2, torch.int32, (m, Hh, Ww), "mask_centers dist2")
+        if m == 0:
+            return out
+        u8 = 1 if masks.dtype == torch.uint8 else 0
+        slots = self.empty(m, dtype=torch.int64)
+        if dist2 is not None:
+            chunks = [(0, m, 0)]
+        else:
+            ws_fn = self.lib.psalm_mask_distance_workspace
+            ws_fn.restype = c_long
+            chunks = self._plane_chunks(lambda k, h, w: ws_fn(k, h, w) + (k * h * w * 4 if ws_fn(k, h, w) >= 0 else 0), m, Hh, Ww, max_workspace_bytes,
+                                        "mask_centers")
+        if index is None and len(chunks) > 1:
+            index = self._iota(n)
+        for r0, k, nbytes in chunks:
+            idx = self._p(index[r0:r0 + k]) if index is not None else c_void_p(0)
+            if dist2 is None:
+                wsb = int(ws_fn(k, Hh, Ww))
+                blk = self._aligned_ws("mask_centers", nbytes)
+                d = blk[wsb:wsb + k * Hh * Ww * 4].view(torch.int32).view(k, Hh, Ww)
+                rc = self.lib.psalm_mask_distance(self._p(masks), u8, n, Hh, Ww, idx, k, 0, 1, self._p(d), self._p(blk), c_long(wsb), self._stream())
+                self._check(rc, "psalm_mask_distance")
+            else:
+                d = dist2
+            rc = self.lib.psalm_mask_centers(self._p(masks), u8, n, Hh, Ww, idx, k, self._p(d), self._p(slots[r0:r0 + k]), self._p(out[r0:r0 + k]),
+                                             self._stream())
+            self._check(rc, "psalm_mask_centers")
+        return out
+
+    def mask_boundaries(self, masks, index=None, out=None):
+        """masks (n,H,W) float32 | uint8 / bool -> (m,H,W) uint8 of 0 / 1: DAVIS's seg2bmap at the mask's own size (a pixel that differs from its right,
+        lower or lower-right neighbour; the last row looks right, the last column down, the last pixel is 0): psalm_mask_boundaries."""
+        masks, n, Hh, Ww, m = self._distance_args(masks, index, "mask_boundaries")
+        out = self.empty(m, Hh, Ww, dtype=torch.uint8) if out is None else self._want(out, torch.uint8, (m, Hh, Ww), "mask_boundaries out")
+        if m:
+            rc = self.lib.psalm_mask_boundaries(self._p(masks), 1 if masks.dtype == torch.uint8 else 0, n, Hh, Ww, self._p(index), m, self._p(out),
+                                                self._stream())
+            self._check(rc, "psalm_mask_boundaries")
+        return out
+
+    def boundary_counts(self, pred, gt, pair_pred, pair_gt, bound, pred_index=None, gt_index=None):
+        """pred (n,H,W), gt (k,H,W) float32 | uint8 / bool, pair_pred / pair_gt (P) i32 on the device -> counts (P,4) i64 = [n_fg, n_gt, fg_match,
+        gt_match] of DAVIS's boundary F per pair: psalm_boundary_counts.  pred_index / gt_index (i32 on the device): the planes that take part
+        (the pairs then index into these lists), default all.  0 <= bound <= 32767: a boundary pixel matches when the other boundary has a pixel
+        within dy^2 + dx^2 <= bound^2.  Boundary and near maps are made once per plane; the workspace holds two bytes per pixel of them."""
+        pred, n_p, Hh, Ww, mp = self._distance_args(pred, pred_index, "boundary_counts")
+        gt, n_t, Ht, Wt, mt = self._distance_args(gt, gt_index, "boundary_counts")
+        if (Hh, Ww) != (Ht, Wt):
+            raise PsalmHipError(f"boundary_counts: predictions of {Hh} x {Ww} against targets of {Ht} x {Wt}")
+        if isinstance(bound, (bool, np.bool_)) or not isinstance(bound, (int, np.integer)) or not 0 <= int(bound) <= self.BOUNDARY_MAX_BOUND:
+            raise PsalmHipError(f"boundary_counts: bound = {bound!r} (an integer, 0 <= bound <= {self.BOUNDARY_MAX_BOUND})")
+        if not torch.is_tensor(pair_pred) or not torch.is_tensor(pair_gt) or pair_pred.dim() != 1 or pair_pred.shape != pair_gt.shape:
+            raise PsalmHipError("boundary_counts: pair_pred / pair_gt (P) int32 of one length")
+        P = int(pair_pred.numel())
+        self._want(pair_pred, torch.int32, (P,), "boundary_counts pair_pred")
+        self._want(pair_gt, torch.int32, (P,), "boundary_counts pair_gt")
+        if P > 65535 or mp + mt > 65535:
+            raise PsalmHipError(f"boundary_counts: {P} pairs over {mp} + {mt} planes (at most 65535 pairs, 65535 planes)")
+        counts = self.empty(P, 4, dtype=torch.int64)
+        if P == 0:
+            return counts
+        ws_fn = self.lib.psalm_boundary_counts_workspace
+        ws_fn.restype = c_long
+        nbytes = int(ws_fn(mp, mt, Hh, Ww))
+        ws = self._aligned_ws("boundary_counts", nbytes)
+        rc = self.lib.psalm_boundary_counts(self._p(pred), 1 if pred.dtype == torch.uint8 else 0, n_p, self._p(pred_index), mp,
+                                            self._p(gt), 1 if gt.dtype == torch.uint8 else 0, n_t, self._p(gt_index), mt, Hh, Ww,
+                                            self._p(pair_pred), self._p(pair_gt), P, int(bound), self._p(counts), self._p(ws), c_long(nbytes), self._stream())
+        self._check(rc, "psalm_boundary_counts")
+        return counts
 
     def _iota(self, n):
         """0 .. n - 1 as int32 on the device (cached per length)"""

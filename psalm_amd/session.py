@@ -505,7 +505,7 @@ class SessionMixin:
                 class_name_embedding_indices=None, cls_indices=None, token_refer_id=None, refer_embedding_indices=None, is_thing_list=None,
                 labels=None, region_point_sampler: Callable = default_region_point_sampler, postprocess: bool = True,
                 stages: Optional[dict] = None, regions=None, region_index_sampler: Callable = default_region_index_sampler, pick: bool = True,
-                outlines: bool = False):
+                outlines: bool = False, centers: bool = False):
         """N >= 1 prompts of the model's task on the session's image: what `eval_seg` returns for a batch of N copies of that image with these
         prompts (a list of N result dicts), without running the vision side again and with a Phi pass over the rows behind the shared prefix
         only.  Prompt-side keywords as eval_seg; `seg_info`: per prompt (region masks / ground truth under "instances", geometry), default the
@@ -531,18 +531,21 @@ class SessionMixin:
         seg_info carries `instances.gt_masks`, and `pick=True` adds `picked_query` (R) int64, `picked_scores` (R) float32, `picked_masks`
         (R, H, W) uint8 (device tensors): per region the first arg-max of `instances.scores` and that query's mask -- and, with the model's
         `mask_boxes` switch on, `picked_boxes` (R, 4) float32 / `picked_areas` (R) int32 of those masks.  `outlines=True` (with `pick`) adds
-        `picked_outlines`: evalout.mask_outlines of `picked_masks` (connectivity 8), the polygons of those masks as device tables."""
+        `picked_outlines`: evalout.mask_outlines of `picked_masks` (connectivity 8), the polygons of those masks as device tables.
+        `centers=True` (with `pick`) adds `picked_centers` (R, 3) int32 on the device: evalout.mask_centers of `picked_masks`, per region
+        [y, x, dist2] of the mask's pixel deepest inside ([-1, -1, 0]: an empty mask) -- (y, x) is a {"points": [(y, x)]} prompt of the next call.
+        It is computed behind everything else; anything but a bool raises ValueError."""
         kw = dict(input_ids=input_ids, attention_mask=attention_mask, seg_info=seg_info, class_name_ids=class_name_ids,
                   class_name_embedding_indices=class_name_embedding_indices, cls_indices=cls_indices, token_refer_id=token_refer_id,
                   refer_embedding_indices=refer_embedding_indices, is_thing_list=is_thing_list, regions=regions)
         return self._segment_requests([(session, kw)], grouped=False, postprocess=postprocess, stages=stages,
                                       region_point_sampler=region_point_sampler, region_index_sampler=region_index_sampler, pick=pick,
-                                      outlines=outlines)[0]
+                                      outlines=outlines, centers=centers)[0]
 
     @torch.no_grad()
     def segment_many(self, requests, *, postprocess: bool = True, region_point_sampler: Callable = default_region_point_sampler,
                      stages: Optional[dict] = None, region_index_sampler: Callable = default_region_index_sampler, pick: bool = True,
-                     outlines: bool = False):
+                     outlines: bool = False, centers: bool = False):
         """Prompts on SEVERAL images in one Phi pass: `requests` is a list of (session, kwargs) pairs, kwargs what `segment(session, **kwargs)` takes
         for the prompt side (input_ids, attention_mask, seg_info, class_name_ids, ..., is_thing_list).  Returns one list per request, each what
         `segment(session, **kwargs)` returns.  Every request obeys segment's rules on its own (session of this model and weights version, its
@@ -553,15 +556,16 @@ class SessionMixin:
         predictor and post-processing run per prompt from its own session.
         Region task: `region_point_sampler` is called request by request in list order, inside a request prompt by prompt and region by region --
         the order a loop of `segment` calls over `requests` draws in.
-        A request's kwargs may carry `regions` (and `pick`, `outlines`) as `segment` takes them: the prompt masks are made per request on the device, ONE read-back
+        A request's kwargs may carry `regions` (and `pick`, `outlines`, `centers`) as `segment` takes them: the prompt masks are made per request on the device, ONE read-back
         brings the pixel totals of all requests, and `region_index_sampler` is called request by request, prompt by prompt, region by region.  Either
         every region request of a call gives `regions` or none does (the two paths draw from the sampler at different points of the call).
         `stages`: filled with the suffix rows' `inputs_embeds` / `hidden_states` ((N, S, hidden), N = all prompts in request order), `prefix_lens`
         (per prompt) and `lengths`."""
         return self._segment_requests(list(requests), grouped=True, postprocess=postprocess, stages=stages, region_point_sampler=region_point_sampler,
-                                      region_index_sampler=region_index_sampler, pick=pick, outlines=outlines)
+                                      region_index_sampler=region_index_sampler, pick=pick, outlines=outlines, centers=centers)
 
-    def _segment_requests(self, requests, *, grouped: bool, postprocess, stages, region_point_sampler, region_index_sampler, pick, outlines=False):
+    def _segment_requests(self, requests, *, grouped: bool, postprocess, stages, region_point_sampler, region_index_sampler, pick, outlines=False,
+                          centers=False):
         """The one pipeline behind `segment` (grouped = False: its one request) and `segment_many` (grouped = True): a list of (session, kwargs)
         pairs -> one list of results per request.  Per request: validation, the region prompts' host side, the suffix splice plan; then the
         prefix caches (one per session), ONE blob with the suffix plans side by side, the region masks / points / features, ONE Phi suffix pass,
@@ -574,6 +578,9 @@ class SessionMixin:
             raise ValueError("segment_many: an empty request list")
         o, w, cfg = self.ops, self.w, self.cfg
         at = (lambda r: f"segment_many: request {r}: ") if grouped else (lambda r: "segment: ")
+        for r, (_, kw) in enumerate(requests):
+            if isinstance(kw, dict) and not isinstance(kw.get("centers", centers), (bool, np.bool_)):
+                raise ValueError(f"{at(r)}centers = {kw.get('centers', centers)!r} (True or False)")
         plans, arrays = [], {}
         any_regions = False
         rps = []                                                  # per request: the plan of its `regions`, or None
@@ -750,6 +757,9 @@ class SessionMixin:
                     if picked and requests[ri][1].get("outlines", outlines):
                         from .evalout import mask_outlines
                         picked["picked_outlines"] = mask_outlines(picked["picked_masks"], connectivity=8, ops=o)
+                    if picked and requests[ri][1].get("centers", centers):
+                        from .evalout import mask_centers
+                        picked["picked_centers"] = mask_centers(picked["picked_masks"], ops=o)
                     res.update(picked)
                 outs.append(res)
             results.append(outs)
@@ -759,7 +769,7 @@ class SessionMixin:
     def segment_everything(self, session: "ImageSession", input_ids, attention_mask=None, *, grid=(8, 8), regions=None, radius=None,
                            iou_thr=0.7, min_area: int = 1, min_score: Optional[float] = None,
                            region_index_sampler: Callable = default_region_index_sampler, min_island: int = 0, max_hole: int = 0,
-                           connectivity: int = 8, outlines: bool = False):
+                           connectivity: int = 8, outlines: bool = False, centers: bool = False):
         """"Show me all the objects": a grid of clicks on the session's image, one mask per object back.  `input_ids` (N, T): region-task prompts
         on the session's image that hold R <region> tokens together, 1 <= R <= 1024.  Either `grid=(gy, gx)` with gy * gx == R -- one click per
         cell at the cell centre ((2 i + 1) h // (2 gy), (2 j + 1) w // (2 gx)) of the original (h, w), dealt to the prompts in row-major order by
@@ -786,7 +796,12 @@ class SessionMixin:
 
         `outlines=True`: the result gains `outlines`, evalout.mask_outlines of the K returned `masks` under the call's `connectivity` -- the
         survivors as polygons (`evalout.outline_polygons` lists them; COCO `segmentation` lists as they stand) -- behind everything else: every
-        other key and every launch in front of it are those of the call without it."""
+        other key and every launch in front of it are those of the call without it.
+
+        `centers=True`: the result gains `centers` (K, 3) int32, evalout.mask_centers of the K returned `masks`: per survivor [y, x, dist2] of the
+        pixel deepest inside it, the image border counted as outside -- a click in the original image's pixels, the space of `regions=`:
+        {"points": [(y, x)]} re-prompts `segment` or starts a `VideoTracker` on that object.  Computed behind everything else (behind
+        `outlines`), with the same guarantee; anything but a bool raises ValueError."""
         from .evalout import iou_fraction
         if self.seg_task != "region":
             raise ValueError(f"segment_everything: clicks are prompts of the region task (this model's seg_task = {self.seg_task!r})")
@@ -801,6 +816,8 @@ class SessionMixin:
                 raise ValueError(f"segment_everything: {name} = {v!r} (an integer >= 0)")
         if isinstance(connectivity, (bool, np.bool_)) or connectivity not in (4, 8):
             raise ValueError(f"segment_everything: connectivity = {connectivity!r} (4 or 8)")
+        if not isinstance(centers, (bool, np.bool_)):
+            raise ValueError(f"segment_everything: centers = {centers!r} (True or False)")
         ids = input_ids[None] if input_ids.dim() == 1 else input_ids
         n_tok = (ids == REGION_TOKEN_INDEX).sum(1).tolist()
         R = int(sum(n_tok))
@@ -831,15 +848,17 @@ class SessionMixin:
         prompts = self._segment_requests([(session, kw)], grouped=False, postprocess=True, stages=None,
                                          region_point_sampler=default_region_point_sampler, region_index_sampler=region_index_sampler, pick=True)[0]
         out = self._everything_dedup(prompts, n_tok, num, den, min_area, min_score, int(min_island), int(max_hole), int(connectivity),
-                                     outlines=bool(outlines))
+                                     outlines=bool(outlines), centers=bool(centers))
         out["prompts"] = prompts
         return out
 
-    def _everything_dedup(self, prompts, n_tok, num, den, min_area, min_score, min_island=0, max_hole=0, connectivity=8, outlines=False):
+    def _everything_dedup(self, prompts, n_tok, num, den, min_area, min_score, min_island=0, max_hole=0, connectivity=8, outlines=False,
+                          centers=False):
         """The device step behind the pipeline: `prompts`, what `segment(..., pick=True)` returned for prompts of n_tok[b] regions each ->
         segment_everything's result without "prompts".  Reads `instances.pred_masks`, `picked_query` and `picked_scores` of every prompt.
         min_island / max_hole > 0: the picked planes are cleaned (psalm_mask_clean) into one (R, H, W) byte buffer, which is packed instead.
-        outlines: behind everything else, the K survivors' masks as polygons (evalout.mask_outlines under `connectivity`)."""
+        outlines: behind everything else, the K survivors' masks as polygons (evalout.mask_outlines under `connectivity`).
+        centers: behind that, the K survivors' deepest pixels (evalout.mask_centers)."""
         o = self.ops
         R = int(sum(n_tok))
         sizes = {tuple(p["instances"].pred_masks.shape[1:]) for p in prompts}
@@ -888,4 +907,7 @@ class SessionMixin:
         if outlines:
             from .evalout import mask_outlines
             out["outlines"] = mask_outlines(masks, connectivity=connectivity, ops=o)
+        if centers:
+            from .evalout import mask_centers
+            out["centers"] = mask_centers(masks, ops=o)
         return out
