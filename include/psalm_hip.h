@@ -47,7 +47,7 @@ const char* psalm_last_error(void);
  *    psalm_causal_attention_f32_split_prepared, psalm_phi_forward_plan, PSALM_TUNE_PHI_ROPE_EPILOGUE.
  * 17: mask outlines and polygon fill: psalm_mask_outline_totals, psalm_mask_outlines (+ _workspace), psalm_mask_fill_polygons (+ _workspace).
  * 18: mask distance maps: psalm_mask_distance (+ _workspace), psalm_mask_centers, psalm_mask_boundaries, psalm_boundary_counts (+ _workspace). */
-#define PSALM_ABI_VERSION 18
+#define PSALM_ABI_VERSION 19
 int psalm_abi_version(void);
 const char* psalm_backend(void); /* "hip-gfx950" */
 
@@ -1000,6 +1000,39 @@ long psalm_boundary_counts_workspace(int mp, int mt, int H, int W);
 int psalm_boundary_counts(const void* pred, int pred_is_u8, int n_pred, const int* pred_index_dev, int mp, const void* gt, int gt_is_u8, int n_gt,
                           const int* gt_index_dev, int mt, int H, int W, const int* pair_pred, const int* pair_gt, int P, int bound,
                           long long* counts, void* workspace, long workspace_bytes, void* stream);
+
+/* ------------------------------------------------------------------------------------------------------------------
+ * Panoptic quality (csrc/panopticq.hip; psalm_amd/evalout.py label_pair_counts / PanopticQuality): panopticapi's pq_compute_single_core on id
+ * maps that are on the device, without the PNG round trip.  Everything is integers but the matched IoU quotients, and those are summed in one
+ * fixed order.  Nothing allocates or synchronises. */
+/* counts (G+2, P+2) i32, OVERWRITTEN: the joint histogram of two id maps of H x W pixels, 1 <= H * W <= 2^31 - 1.  A map is (H,W) int32, or
+ * (H,W,3) bytes when its _is_rgb flag is set: id = R + 256 G + 65536 B (panopticapi rgb2id, the inverse of psalm_panoptic_rgb).  gt_ids (G) /
+ * pred_ids (P): int32 on the device, STRICTLY ASCENDING, all > 0 (the caller's contract: the entry cannot see them), 0 <= G, P <= 1023.
+ * The slot of a pixel value v under a table T of length n is 0 when v == 0 (VOID), 1 + k when v == T[k], n + 1 for any other value, negatives
+ * included; counts[a][b] = pixels with gt slot a and pred slot b; the table sums to H * W.
+ * A wavefront aggregates the equal (gt, pred) values of 64 consecutive pixels with ballots (one table add per distinct pair; only the group's
+ * leader searches the id tables, held in LDS); a block accumulates in LDS -- the dense table when ids and table fit 144 KB, else a block-local
+ * open-addressed (key, count) table that falls back to global adds when full -- and flushes once per touched entry.  Integer adds only: the
+ * result does not depend on the order of arrival. */
+int psalm_label_pair_counts(const void* gt, int gt_is_rgb, const int* gt_ids, int G, const void* pred, int pred_is_rgb, const int* pred_ids, int P,
+                            int H, int W, int* counts, void* stream);
+/* One image's match, accumulated: counts (G+2, P+2) as above; gt_cat (G) / pred_cat (P): category slots in [0, C), 1 <= C <= 4096; gt_crowd (G):
+ * 0 / 1; pred_crowd_slot (P): the gt slot 1..G of the crowd segment of that prediction's category, or -1 -- all int32 on the device.
+ * Accumulators (device, persistent, 8-byte aligned, zeroed by the caller once): stat (C,3) i64 = [tp, fp, fn], iou (C) f64, notes (4) i64 =
+ * [images, unlisted gt pixels, unlisted pred pixels, listed pred segments with no pixel].
+ * With area_gt[g] = sum of row g, area_pred[p] = sum of column p (all slots):
+ *   match  g = 1..G ascending, inside it p = 1..P ascending; pairs with counts[g][p] == 0, gt_crowd[g-1] set or gt_cat[g-1] != pred_cat[p-1]
+ *          are passed over; union = area_pred[p] + area_gt[g] - counts[g][p] - counts[0][p]; a match iff 2 * counts[g][p] > union (integers;
+ *          == iou > 0.5): tp[cat] += 1, iou[cat] += (double)counts[g][p] / (double)union, g and p are matched;
+ *   FN     every g neither matched nor crowd (a listed gt segment without a pixel included): fn[gt_cat] += 1;
+ *   FP     every unmatched p with area_pred[p] > 0: inter = counts[0][p] + (counts[pred_crowd_slot][p] if pred_crowd_slot >= 0);
+ *          2 * inter > area_pred[p]: forgiven, else fp[pred_cat] += 1;  a listed p with area_pred[p] == 0 counts in notes[3] only;
+ *   notes  [0] += 1, [1] += the sum of row G + 1, [2] += the sum of column P + 1.
+ * The float64 additions happen in exactly that (g, p) order, by one thread, image after image (the search for matches is parallel): with IEEE
+ * division the sums equal a host loop's in np.unique's order of gt_id * 256^3 + pred_id bit for bit.  A category slot outside [0, C) or a crowd
+ * slot outside [1, G] makes its segment count nothing. */
+int psalm_pq_accumulate(const int* counts, int G, int P, const int* gt_cat, const int* gt_crowd, const int* pred_cat, const int* pred_crowd_slot,
+                        int C, long long* stat, double* iou, long long* notes, void* stream);
 
 #ifdef __cplusplus
 }

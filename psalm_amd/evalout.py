@@ -26,6 +26,8 @@ with one tiny RCCL all-reduce (`psalm_amd.dist.reduce_metrics`, the role of Aver
     mask_boundaries(masks)                        DAVIS seg2bmap at the mask's own size
     boundary_counts(pred, gt, pairs, bound)       DAVIS f_measure's integers per pair; boundary_f(counts) -> precision, recall, F; davis_bound(shape)
     JFMeters                                      DAVIS J&F bookkeeping beside IoUMeters (J from iou_counts, F from boundary_counts) + all-reduce
+    label_pair_counts(gt, gt_ids, pred, pred_ids) panopticapi pq_compute_single_core's np.unique(gt * 256^3 + pred): the overlap table of two id maps
+    PanopticQuality(categories).update(...)       panoptic_evaluation.py:179-221 + panopticapi pq_compute: PQ / SQ / RQ without the PNG round trip
     coco_instance_records(instances, image_id)    detectron2 instances_to_coco_json (instance_evaluation.py) -> the COCO result records
 """
 from __future__ import annotations
@@ -532,14 +534,166 @@ class JFMeters:
         return {"J": j, "F": f, "J&F": (j + f) / 2, "n": int(self.sum[2])}
 
 
-def compact_results(result: dict, gt_sem: Optional[torch.Tensor] = None, conf: Optional[ConfusionMatrix] = None, ops=None) -> dict:
+def _id_map(o, m, what: str) -> torch.Tensor:
+    """An id map for the pair-count kernel: a tensor or array on host or device, (H,W) of any integer type (held as int32) or the panoptic PNG's
+    (H,W,3) uint8 -> contiguous on the device."""
+    if isinstance(m, np.ndarray):
+        if m.dtype == np.uint32:
+            m = m.astype(np.int64)
+        m = torch.from_numpy(np.ascontiguousarray(m))
+    if not torch.is_tensor(m):
+        raise H.PsalmHipError(f"{what}: a tensor or array, got {type(m)}")
+    if m.dim() == 3 and m.shape[2] == 3 and m.dtype == torch.uint8:
+        return m.to(o.device).contiguous()
+    if m.dim() != 2 or m.dtype not in (torch.int32, torch.int64, torch.int16, torch.uint8):
+        raise H.PsalmHipError(f"{what}: an (H,W) integer id map or its (H,W,3) uint8 rgb form, got {m.dtype} {tuple(m.shape)}")
+    return m.to(o.device, torch.int32).contiguous()
+
+
+def _sorted_ids(ids, what: str) -> Tuple[np.ndarray, np.ndarray]:
+    """any integer sequence -> (the ids ascending as int32, the permutation that sorts them); duplicates, values <= 0 or >= 2^31, more than 1023:
+    ValueError"""
+    ids = ids.cpu().tolist() if torch.is_tensor(ids) else ids.tolist() if isinstance(ids, np.ndarray) else list(ids)
+    if any(isinstance(v, (bool, np.bool_)) or not isinstance(v, (int, np.integer)) for v in ids):
+        raise ValueError(f"{what}: a flat sequence of integers")
+    if len(ids) > H.Ops.LABEL_PAIRS_MAX_IDS:
+        raise ValueError(f"{what}: {len(ids)} ids (at most {H.Ops.LABEL_PAIRS_MAX_IDS})")
+    if any(not 0 < int(v) < 2 ** 31 for v in ids):
+        raise ValueError(f"{what}: ids must lie in [1, 2^31 - 1] (0 is VOID)")
+    v = np.array([int(x) for x in ids], dtype=np.int64)
+    order = np.argsort(v, kind="stable")
+    s = v[order]
+    if (np.diff(s) == 0).any():
+        raise ValueError(f"{what}: an id is listed twice")
+    return s.astype(np.int32), order.astype(np.int64)
+
+
+def label_pair_counts(gt, gt_ids, pred, pred_ids, ops=None):
+    """The overlap table of two id maps -- what panopticapi gets from `np.unique(gt * 256^3 + pred, return_counts=True)` -- on the device: gt, pred on
+    host or device, (H,W) integers or the PNG's (H,W,3) uint8 (id = R + 256 G + 65536 B); gt_ids / pred_ids: any integer sequences of distinct ids
+    in [1, 2^31 - 1], at most 1023 each (ValueError otherwise) -> (counts (G+2, P+2) int32 on the device, gt_order, pred_order).  The ids are sorted
+    here: row 1 + k counts the pixels of `gt_ids[gt_order[k]]`, row 0 the value 0 (VOID), the last row every other value; columns likewise for
+    `pred`.  The table sums to H * W.  Nothing is read back."""
+    o = _ops(ops)
+    gs, g_order = _sorted_ids(gt_ids, "label_pair_counts gt_ids")
+    ps, p_order = _sorted_ids(pred_ids, "label_pair_counts pred_ids")
+    tab = torch.from_numpy(np.concatenate((gs, ps))).to(o.device)                                           # one small upload
+    counts = o.label_pair_counts(_id_map(o, gt, "label_pair_counts gt"), tab[:gs.size], _id_map(o, pred, "label_pair_counts pred"), tab[gs.size:],
+                                 check=False)
+    return counts, g_order, p_order
+
+
+class PanopticQuality:
+    """PQ / SQ / RQ of COCO panoptic -- panopticapi's `pq_compute` -- kept on the device beside `ConfusionMatrix`, without the PNG round trip of
+    my_coco_panoptic_evaluator (panoptic_evaluation.py:179-221).  categories: {dataset category id: isthing}; a dict of panopticapi's records
+    ({id: {"isthing": ..}}) is taken too.  `update` per image (two launches, no read-back), `results()` once at the end."""
+
+    def __init__(self, categories: dict, ops=None):
+        self.ops = _ops(ops)
+        self.categories = {int(k): bool(v["isthing"] if isinstance(v, dict) else v) for k, v in categories.items()}
+        C = len(self.categories)
+        if not 1 <= C <= H.Ops.PQ_MAX_CATEGORIES:
+            raise ValueError(f"PanopticQuality: {C} categories (1..{H.Ops.PQ_MAX_CATEGORIES})")
+        self._slot = {c: i for i, c in enumerate(self.categories)}
+        dev = self.ops.device
+        self.stat = torch.zeros(C, 3, dtype=torch.int64, device=dev)      # [tp, fp, fn]
+        self.iou = torch.zeros(C, dtype=torch.float64, device=dev)
+        self.notes = torch.zeros(4, dtype=torch.int64, device=dev)        # [images, unlisted gt pixels, unlisted pred pixels, empty listed preds]
+
+    def _cat_slot(self, cat, what):
+        try:
+            return self._slot[int(cat)]
+        except KeyError:
+            raise ValueError(f"PanopticQuality.update: {what} category {cat!r} is not one of the meter's categories") from None
+
+    def update(self, pred, pred_segments_info, gt, gt_segments_info, category_ids: Optional[Sequence[int]] = None) -> None:
+        """One image: pred = `result["panoptic_seg"][0]` with its `segments_info` list ({"id", "category_id", ..}; category_ids: the contiguous class
+        index -> dataset category id table, as in `coco_instance_records`), gt = the ground truth's id map or its RGB PNG array with the COCO panoptic
+        JSON's records ({"id", "category_id", "iscrowd"}).  One small upload (sorted id tables, category slots, crowd flags, each prediction's crowd
+        slot), `psalm_label_pair_counts`, `psalm_pq_accumulate`; nothing is read back.  A category outside the meter's: ValueError."""
+        o = self.ops
+        gs, g_order = _sorted_ids([s["id"] for s in gt_segments_info], "PanopticQuality.update gt ids")
+        ps, p_order = _sorted_ids([s["id"] for s in pred_segments_info], "PanopticQuality.update prediction ids")
+        G, P = gs.size, ps.size
+        g_slot_of = np.empty(G, np.int64)
+        g_slot_of[g_order] = 1 + np.arange(G)                            # JSON position -> gt slot
+        g_cat = np.array([self._cat_slot(s["category_id"], "ground-truth") for s in gt_segments_info], dtype=np.int64).reshape(-1)
+        g_crowd = np.array([1 if int(s.get("iscrowd", 0)) == 1 else 0 for s in gt_segments_info], dtype=np.int64).reshape(-1)
+        crowd_slot = {}                                                  # panopticapi's crowd_labels_dict: the LAST crowd segment of a category wins
+        for k in range(G):
+            if g_crowd[k]:
+                crowd_slot[int(g_cat[k])] = int(g_slot_of[k])
+        p_cat = np.array([self._cat_slot(category_ids[int(s["category_id"])] if category_ids is not None else s["category_id"], "prediction")
+                          for s in pred_segments_info], dtype=np.int64).reshape(-1)
+        p_crowd = np.array([crowd_slot.get(int(c), -1) for c in p_cat], dtype=np.int64).reshape(-1)
+        tab = torch.from_numpy(np.concatenate((gs, ps, g_cat[g_order], g_crowd[g_order], p_cat[p_order], p_crowd[p_order])).astype(np.int32)).to(o.device)
+        cut = np.cumsum([0, G, P, G, G, P, P]).tolist()
+        t_gs, t_ps, t_gcat, t_gcrowd, t_pcat, t_pcrowd = (tab[a:b] for a, b in zip(cut[:-1], cut[1:]))
+        counts = o.label_pair_counts(_id_map(o, gt, "PanopticQuality.update gt"), t_gs, _id_map(o, pred, "PanopticQuality.update pred"), t_ps, check=False)
+        o.pq_accumulate(counts, t_gcat, t_gcrowd, t_pcat, t_pcrowd, self.stat, self.iou, self.notes)
+
+    def all_reduce(self, device=None) -> None:
+        """SUM over ranks as ONE small all-reduce (`psalm_amd.dist.reduce_metrics`) of a (C,4) float64 [tp, fp, fn, iou] block plus the notes; the
+        counts stay exact below 2^53.  `device` as in IoUMeters.all_reduce."""
+        import torch.distributed as dist
+        from .dist import reduce_metrics
+        if device is None and dist.is_available() and dist.is_initialized() and dist.get_backend() == "nccl":
+            device = torch.device("cuda", torch.cuda.current_device())
+        C = len(self.categories)
+        t = torch.cat((self.stat.double(), self.iou[:, None]), dim=1).reshape(-1)
+        t = torch.cat((t, self.notes.double()))
+        t = reduce_metrics(t.to(device) if device is not None else t.clone()).double().to(self.ops.device)
+        block = t[:4 * C].reshape(C, 4)
+        self.stat = block[:, :3].round().to(torch.int64).contiguous()
+        self.iou = block[:, 3].contiguous()
+        self.notes = t[4 * C:].round().to(torch.int64).contiguous()
+
+    def results(self, strict: bool = True) -> dict:
+        """panopticapi's `pq_compute` result from ONE read-back of the accumulators: {"All" | "Things" | "Stuff": {"pq", "sq", "rq", "n"}, "per_class":
+        {category id: {"pq", "sq", "rq"}}, "notes": {"images", "unlisted_gt_pixels", "unlisted_pred_pixels", "empty_pred_segments"}} in
+        `pq_average`'s arithmetic (a class with tp + fp + fn == 0 is left out of n and reads 0; sq = 0 when tp == 0; a group without any class gives
+        0 where panopticapi divides by zero).  strict=True: pixels of a prediction id that its segments_info does not list raise, as panopticapi
+        does."""
+        C = len(self.categories)
+        flat = torch.cat((self.stat.double().reshape(-1), self.iou, self.notes.double())).cpu().numpy()      # the one read-back (counts < 2^53)
+        stat = np.rint(flat[:3 * C]).astype(np.int64).reshape(C, 3)
+        iou = flat[3 * C:4 * C]
+        notes = np.rint(flat[4 * C:]).astype(np.int64)
+        note = {"images": int(notes[0]), "unlisted_gt_pixels": int(notes[1]), "unlisted_pred_pixels": int(notes[2]), "empty_pred_segments": int(notes[3])}
+        if strict and note["unlisted_pred_pixels"]:
+            raise ValueError(f"PanopticQuality: {note['unlisted_pred_pixels']} prediction pixels carry an id that segments_info does not list")
+        out = {"per_class": {}, "notes": note}
+        for name, isthing in (("All", None), ("Things", True), ("Stuff", False)):
+            pq = sq = rq = 0.0
+            n = 0
+            for cat, thing in self.categories.items():
+                if isthing is not None and thing != isthing:
+                    continue
+                k = self._slot[cat]
+                tp, fp, fn, s = int(stat[k, 0]), int(stat[k, 1]), int(stat[k, 2]), float(iou[k])
+                if tp + fp + fn == 0:
+                    res = {"pq": 0.0, "sq": 0.0, "rq": 0.0}
+                else:
+                    n += 1
+                    res = {"pq": s / (tp + 0.5 * fp + 0.5 * fn), "sq": s / tp if tp != 0 else 0.0, "rq": tp / (tp + 0.5 * fp + 0.5 * fn)}
+                    pq, sq, rq = pq + res["pq"], sq + res["sq"], rq + res["rq"]
+                if isthing is None:
+                    out["per_class"][cat] = res
+            out[name] = {"pq": pq / n if n else 0.0, "sq": sq / n if n else 0.0, "rq": rq / n if n else 0.0, "n": n}
+        return out
+
+
+def compact_results(result: dict, gt_sem: Optional[torch.Tensor] = None, conf: Optional[ConfusionMatrix] = None, ops=None,
+                    pq: Optional[PanopticQuality] = None, gt_panoptic=None, category_ids: Optional[Sequence[int]] = None) -> dict:
     """What the reference's panoptic / semantic / instance evaluators keep of ONE eval_seg result (panoptic_evaluation.py:114-145,179-222;
     instance masks as COCO RLE, region_segmentation.py:282), produced on the device, so that KBs..MBs instead of ~1 GB cross PCIe:
         "sem_labels"   (H,W) int32          from result["sem_seg"]           (+ conf.update(labels, gt_sem) when both are given)
         "panoptic_rgb" (H,W,3) uint8, "segments_info"   from result["panoptic_seg"]
         "instances"    {"rle": [...], "scores": (n,), "pred_classes": (n,)}  from result["instances"]
                        (+ "boxes" (n,4), "areas" (n,) when the result was made under `PSALM.mask_boxes = True`)
-    Keys follow what the result holds (semantic-only / instance-only tasks give the matching subset)."""
+    Keys follow what the result holds (semantic-only / instance-only tasks give the matching subset).
+    pq + gt_panoptic = (ground-truth id map or RGB PNG array, its segments_info): when both are given and the result holds `panoptic_seg`, the
+    image is scored on the device as well -- `pq.update(pan, info, *gt_panoptic, category_ids=category_ids)`; nothing else changes."""
     o = _ops(ops)
     out = {}
     if "sem_seg" in result:
@@ -550,6 +704,8 @@ def compact_results(result: dict, gt_sem: Optional[torch.Tensor] = None, conf: O
         pan, info = result["panoptic_seg"]
         out["panoptic_rgb"] = panoptic_png_rgb(pan, ops=o)
         out["segments_info"] = info
+        if pq is not None and gt_panoptic is not None:
+            pq.update(pan, info, gt_panoptic[0], gt_panoptic[1], category_ids=category_ids)
     if "instances" in result and getattr(result["instances"], "pred_masks", None) is not None:
         inst = result["instances"]
         out["instances"] = {"rle": masks_to_rle(inst.pred_masks, ops=o), "scores": inst.scores}

@@ -49,7 +49,7 @@ def _dt(t: torch.Tensor) -> int:
         raise PsalmHipError(f"unsupported dtype {t.dtype} (float32 / bfloat16 only)")
 
 
-ABI_VERSION = 18       # == PSALM_ABI_VERSION of include/psalm_hip.h (tests/test_0_abi.py compares the two and the built library's answer)
+ABI_VERSION = 19       # == PSALM_ABI_VERSION of include/psalm_hip.h (tests/test_0_abi.py compares the two and the built library's answer)
 
 
 class _ProfiledLib:
@@ -2351,6 +2351,78 @@ class Ops:
                                             self._p(pair_pred), self._p(pair_gt), P, int(bound), self._p(counts), self._p(ws), c_long(nbytes), self._stream())
         self._check(rc, "psalm_boundary_counts")
         return counts
+
+    # ------------------------------------------------------------------ panoptic quality (csrc/panopticq.hip)
+    LABEL_PAIRS_MAX_IDS = 1023
+    PQ_MAX_CATEGORIES = 4096
+
+    def _id_map(self, t, what):
+        """an id map as the kernels read it: (H,W) int32, or (H,W,3) uint8 = the panoptic PNG's rgb -> (tensor, is_rgb, H, W)"""
+        if not torch.is_tensor(t) or not ((t.dim() == 2 and t.dtype == torch.int32) or (t.dim() == 3 and t.shape[2] == 3 and t.dtype == torch.uint8)):
+            raise PsalmHipError(f"{what}: an (H,W) int32 id map or its (H,W,3) uint8 rgb form, got {getattr(t, 'dtype', type(t))} "
+                                f"{tuple(getattr(t, 'shape', ()))}")
+        if not t.is_contiguous():
+            raise PsalmHipError(f"{what}: the map must be contiguous")
+        return t, 1 if t.dim() == 3 else 0, int(t.shape[0]), int(t.shape[1])
+
+    def _id_table(self, ids, check, what):
+        if not torch.is_tensor(ids) or ids.dim() != 1 or ids.dtype != torch.int32 or not ids.is_contiguous():
+            raise PsalmHipError(f"{what}: a contiguous (n) int32 tensor, got {getattr(ids, 'dtype', type(ids))} {tuple(getattr(ids, 'shape', ()))}")
+        n = int(ids.numel())
+        if n > self.LABEL_PAIRS_MAX_IDS:
+            raise PsalmHipError(f"{what}: {n} ids (at most {self.LABEL_PAIRS_MAX_IDS})")
+        if check and n:
+            v = ids.cpu().numpy().astype(np.int64)
+            if v[0] <= 0 or (np.diff(v) <= 0).any():
+                raise PsalmHipError(f"{what}: ids must be > 0 and strictly ascending")
+        return n
+
+    def label_pair_counts(self, gt, gt_ids, pred, pred_ids, out=None, check=True):
+        """gt, pred: id maps of one size, each (H,W) int32 or (H,W,3) uint8 (id = R + 256 G + 65536 B); gt_ids (G), pred_ids (P): int32 on the device,
+        strictly ascending, > 0, at most 1023 each -> counts (G+2, P+2) i32, overwritten: counts[a][b] = pixels whose gt value has slot a and whose
+        pred value has slot b (slot 0: the value 0 = VOID; 1 + k: table entry k; last: any other value): psalm_label_pair_counts.  check=True reads
+        the two tables back to verify their order (a caller that sorted them on the host passes False: the kernel's binary search relies on it).
+        `out` may be given (a view of a caller-owned block)."""
+        gt, g_rgb, Hh, Ww = self._id_map(gt, "label_pair_counts gt")
+        pred, p_rgb, Hp, Wp = self._id_map(pred, "label_pair_counts pred")
+        if (Hh, Ww) != (Hp, Wp):
+            raise PsalmHipError(f"label_pair_counts: a ground truth of {Hh} x {Ww} against a prediction of {Hp} x {Wp}")
+        if not 1 <= Hh * Ww <= 2 ** 31 - 1:
+            raise PsalmHipError(f"label_pair_counts: {Hh} x {Ww} pixels (1 <= H * W <= 2^31 - 1)")
+        G = self._id_table(gt_ids, check, "label_pair_counts gt_ids")
+        P = self._id_table(pred_ids, check, "label_pair_counts pred_ids")
+        counts = self.empty(G + 2, P + 2, dtype=torch.int32) if out is None else self._want(out, torch.int32, (G + 2, P + 2), "label_pair_counts out")
+        rc = self.lib.psalm_label_pair_counts(self._p(gt), g_rgb, self._p(gt_ids), G, self._p(pred), p_rgb, self._p(pred_ids), P, Hh, Ww,
+                                              self._p(counts), self._stream())
+        self._check(rc, "psalm_label_pair_counts")
+        return counts
+
+    def pq_accumulate(self, counts, gt_cat, gt_crowd, pred_cat, pred_crowd_slot, stat, iou, notes):
+        """counts (G+2, P+2) i32 of `label_pair_counts`; gt_cat, gt_crowd (G), pred_cat, pred_crowd_slot (P) i32 on the device (category slots in
+        [0, C), crowd flags 0 / 1, per prediction the gt slot 1..G of its category's crowd segment or -1); the accumulators stat (C,3) i64 = [tp, fp,
+        fn], iou (C) f64, notes (4) i64 are added to in place: psalm_pq_accumulate (panopticapi's pq_compute_single_core for one image; the IoU
+        sums are added in its own order by one thread, so they are reproducible bit for bit).  Returns None."""
+        if not torch.is_tensor(counts) or counts.dim() != 2 or counts.shape[0] < 2 or counts.shape[1] < 2:
+            raise PsalmHipError(f"pq_accumulate: counts (G+2, P+2) int32, got {tuple(getattr(counts, 'shape', ()))}")
+        G, P = int(counts.shape[0]) - 2, int(counts.shape[1]) - 2
+        if G > self.LABEL_PAIRS_MAX_IDS or P > self.LABEL_PAIRS_MAX_IDS:
+            raise PsalmHipError(f"pq_accumulate: {G} x {P} listed segments (at most {self.LABEL_PAIRS_MAX_IDS} per side)")
+        self._want(counts, torch.int32, (G + 2, P + 2), "pq_accumulate counts")
+        for t, n, what in ((gt_cat, G, "gt_cat"), (gt_crowd, G, "gt_crowd"), (pred_cat, P, "pred_cat"), (pred_crowd_slot, P, "pred_crowd_slot")):
+            if not torch.is_tensor(t):
+                raise PsalmHipError(f"pq_accumulate {what}: an int32 tensor on the device")
+            self._want(t, torch.int32, (n,), "pq_accumulate " + what)
+        if not torch.is_tensor(stat) or stat.dim() != 2:
+            raise PsalmHipError("pq_accumulate: stat (C,3) int64")
+        C = int(stat.shape[0])
+        if not 1 <= C <= self.PQ_MAX_CATEGORIES:
+            raise PsalmHipError(f"pq_accumulate: {C} categories (1..{self.PQ_MAX_CATEGORIES})")
+        self._want(stat, torch.int64, (C, 3), "pq_accumulate stat")
+        self._want(iou, torch.float64, (C,), "pq_accumulate iou")
+        self._want(notes, torch.int64, (4,), "pq_accumulate notes")
+        rc = self.lib.psalm_pq_accumulate(self._p(counts), G, P, self._p(gt_cat), self._p(gt_crowd), self._p(pred_cat), self._p(pred_crowd_slot), C,
+                                          self._p(stat), self._p(iou), self._p(notes), self._stream())
+        self._check(rc, "psalm_pq_accumulate")
 
     def _iota(self, n):
         """0 .. n - 1 as int32 on the device (cached per length)"""
